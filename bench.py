@@ -25,10 +25,20 @@ the data path is the filterbank's distribution from rank 0 - DESIGN.md §5):
 step per collective (``broadcast`` and ``scatter_allgather``).
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus ``roofline``
-(dominant kernel, HIP events on its launch stream; HBM counter traffic from the PMC
-summary committed under profiles/), ``clean`` (the C4 cleaning pass, configs[3]) and
-``cpu_baseline`` (the C oracle = a port of the reference's numba search, OpenMP over
-trials, timed on a bounded trial sample on the host's cores).
+(dominant kernel, HIP events on its launch stream inside the timed steps; HBM counter
+traffic from the PMC summary committed under profiles/).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+result line.  ``--dump-outputs DIR`` also writes what the last timed step returned
+(``max``, ``std``, ``snr``, ``rebin`` per trial of the whole grid) as ``DIR/<name>.npy``
+(float64); the input is seeded, so two builds can be compared output for output.
+``--full`` adds everything that takes runs of its own: ``acc_f64`` (the same search at
+reference precision), ``clean`` (the C4 cleaning pass, configs[3]), ``cpu_baseline``
+(the C oracle = a port of the reference's numba search, OpenMP over trials, timed on a
+bounded trial sample on the host's cores), ``c3_strong`` (configs[2] on this GPU), and
+with N > 1 ``multi_gpu`` (the exchanges alone), ``phases`` (one extra step with events
+around its phases) and ``single_gpu_same_workload``; the ``--no-*`` switches drop single
+legs of it.
 """
 import argparse
 import json
@@ -374,6 +384,13 @@ def exchange_bench(x, plan, outs, ws, dev, chunks, decomposition="dm"):
     return res
 
 
+def dump_outputs(path, arrays):
+    """``path/<name>.npy`` for each per-trial array of the last timed step (float64)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -398,6 +415,12 @@ def main():
     ap.add_argument("--shard", type=int, default=0,
                     help="with --scaling strong on one GPU: search only rank 0's slice of an N-way split "
                          "(e.g. --config C3 --scaling strong --shard 8: the 625-trial shard of the 8-GPU run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: acc_f64, clean (C4), the CPU baseline, c3_strong; "
+                         "N > 1: the exchanges alone, the per-phase step, the one-GPU reference")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's per-trial max, std, snr and rebin of the "
+                         "whole grid as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ref", action="store_true",
                     help="N > 1 strong split: skip the one-GPU run of the same workload on rank 0")
@@ -417,6 +440,8 @@ def main():
                     help="time even with PU_* / PULSARUTILS_* tuning variables set (sweeps only: the line "
                          "is marked invalid)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     knobs = knob_env()
     if knobs and not args.allow_knobs:
         sys.exit(f"bench.py: refusing to time with tuning variables set {knobs} (they reshape the kernels or "
@@ -490,7 +515,7 @@ def main():
     gathered = torch.empty((world * 4, chunk), dtype=torch.float64, device=dev)  # rank-major (4, chunk) blocks
 
     bcast = None
-    if world > 1:
+    if world > 1 and args.full:
         bcast = exchange_bench(x, plan, outs, ws, dev, args.bcast_chunks, args.decomposition if pipelined else "dm")
         if rank == 0:
             log(f"exchange {bcast}")
@@ -542,11 +567,22 @@ def main():
         elapsed = float(tt.item())
     ms_per_step = elapsed / args.steps * 1e3
 
+    # what the last timed step returned, per trial of the whole grid (rank 0's view)
+    if world > 1:
+        g4 = gathered.view(world, 4, chunk)
+        stats_all = np.concatenate([g4[r, :, :shard_bounds(dms_all.size, world, r)[1]
+                                       - shard_bounds(dms_all.size, world, r)[0]].cpu().numpy()
+                                    for r in range(world)], axis=1)
+    else:
+        stats_all = np.stack([o.cpu().numpy().astype(np.float64) for o in outs])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("max", "std", "snr", "rebin"), stats_all)))
+
     # N > 1, pipelined: one more (untimed) step with HIP events around its phases - the
     # exchange, unpack and tile searches per chunk, the finalize, the gather - so a scaling
     # run explains itself; per phase the max over ranks
     phase_ms = None
-    if pipelined:
+    if pipelined and args.full:
         from pulsarutils.parallel import PhaseEvents
         pe = PhaseEvents()
         dist.barrier()
@@ -566,12 +602,7 @@ def main():
                     "rank0": mine, "max_over_ranks": {k: round(float(allv[:, i].max()), 4) for i, k in enumerate(keys)}}
 
     # spot check: best trial of the whole grid (rank 0's view of the gathered S/N)
-    if world > 1:
-        snr_all = np.concatenate([gathered.view(world, 4, chunk)[r, 2, :shard_bounds(dms_all.size, world, r)[1]
-                                           - shard_bounds(dms_all.size, world, r)[0]].cpu().numpy()
-                                  for r in range(world)])
-    else:
-        snr_all = outs[2].cpu().numpy()
+    snr_all = stats_all[2]
     best_dm = float(dms_all[np.argmax(snr_all)])
 
     total_samples = dms_all.size * cfg.nsamples
@@ -632,7 +663,7 @@ def main():
     # step; the other ranks wait), so the line carries its own one-GPU reference - the N = 1
     # headline is C2 (configs[1]), a different workload
     ref1 = None
-    if pipelined and not args.no_ref:
+    if pipelined and args.full and not args.no_ref:
         if rank == 0:
             log("one-GPU reference (the whole grid on rank 0) ...")
             sh_all = _hip.shift_table(cfg.nchan, dms_all, cfg.start_freq, cfg.bandwidth, cfg.tsamp)
@@ -655,19 +686,20 @@ def main():
         dist.barrier()
 
     f64 = None
-    if rank == 0 and world == 1 and not args.no_acc_f64 and args.acc == "native" and cfg.dtype != "f64":
+    if (args.full and rank == 0 and world == 1 and not args.no_acc_f64 and args.acc == "native"
+            and cfg.dtype != "f64"):
         log("acc_f64 ...")
         f64 = acc_f64_bench(x, dms, cfg, args.acc_f64_steps)
         log(f"acc_f64 kernel {f64['kernel_ms']:.3f} ms, step {f64['ms_per_step']:.3f} ms")
 
     clean = None
-    if rank == 0 and world == 1 and not args.no_clean:
+    if args.full and rank == 0 and world == 1 and not args.no_clean:
         log("clean (C4) ...")
         clean = clean_bench(dev, args.clean_steps)
         log(f"clean {clean['f32']['renormalize_ms']:.3f} ms f32, {clean['u8']['renormalize_ms']:.3f} ms u8")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         xh = x.cpu().numpy()
         threads = cpu_threads()
@@ -676,7 +708,7 @@ def main():
         log(f"cpu baseline {cpu['value']:.3e} samples/s on {threads} threads ({cpu['cpu_model']})")
 
     c3 = None
-    if not args.no_c3_strong and args.config != "C3" and world == 1:
+    if args.full and not args.no_c3_strong and args.config != "C3" and world == 1:
         del x, ws, outs, plan
         torch.cuda.empty_cache()
         log("c3_strong ...")

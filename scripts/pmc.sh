@@ -11,7 +11,7 @@ mkdir -p $OUT
 if [ -n "$CLEAN" ]; then
   CMD="python3 scripts/bench_clean.py --steps 2 --warmup 1 $*"
 else
-  CMD="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-clean $*"
+  CMD="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-clean $*"
 fi
 SETS=("SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY"
       "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE"

@@ -23,8 +23,8 @@ if [ -z "$NOSMOKE" ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit $?
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 500 python -u bench.py --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-c3-strong > $OUT/prof.log 2>&1 || exit $?
+  timeout -k 10 500 python -u bench.py --full --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-c3-strong > $OUT/prof.log 2>&1 || exit $?
   python3 scripts/warm_stats.py $OUT/prof --skip 1 > $OUT/rocprof_warm_stats.csv || exit $?
 fi
 args_of() {
@@ -41,9 +41,9 @@ for cfg in ${PMC:-}; do
   A=$(args_of $cfg)
   D=$OUT/pmc_$cfg
   mkdir -p $D
-  timeout -k 10 300 python3 -u bench.py $A --steps 3 --warmup 1 --no-cpu-baseline --no-clean --no-c3-strong > $D/bench.json 2> $D/bench.err || exit $?
-  timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/p1 -o run -- python3 bench.py $A --steps 1 --warmup 1 --no-cpu-baseline --no-clean --no-c3-strong > $D/p1.log 2>&1 || exit $?
-  timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/p2 -o run -- python3 bench.py $A --steps 1 --warmup 1 --no-cpu-baseline --no-clean --no-c3-strong > $D/p2.log 2>&1 || exit $?
+  timeout -k 10 300 python3 -u bench.py $A --full --steps 3 --warmup 1 --no-cpu-baseline --no-clean --no-c3-strong > $D/bench.json 2> $D/bench.err || exit $?
+  timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/p1 -o run -- python3 bench.py $A --full --steps 1 --warmup 1 --no-cpu-baseline --no-clean --no-c3-strong > $D/p1.log 2>&1 || exit $?
+  timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/p2 -o run -- python3 bench.py $A --full --steps 1 --warmup 1 --no-cpu-baseline --no-clean --no-c3-strong > $D/p2.log 2>&1 || exit $?
   python3 scripts/pmc_json.py $D $cfg $D/bench.json > $D/pmc_json.log 2>&1 || exit $?
 done
 for cfg in ${LDSC:-}; do
@@ -70,7 +70,7 @@ if [ -n "$MR" ]; then
   # the N > 1 bench path rehearsed with 2 ranks on this one GPU (gloo: both ranks share the
   # device), small config
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus 2 --config C5 --dist-backend gloo --steps 2 --warmup 1 --bcast-chunks 4 \
+    --master-port 29533 bench.py --full --gpus 2 --config C5 --dist-backend gloo --steps 2 --warmup 1 --bcast-chunks 4 \
     > $OUT/mr_bench_c5.json 2> $OUT/mr_bench_c5.err || exit $?
 fi
 if [ -n "$UNPACK" ]; then
@@ -80,7 +80,7 @@ fi
 if [ -n "$CFGS" ]; then
   for cfg in C1 C5 C3 C3_625; do
     A=$(args_of $cfg)
-    timeout -k 10 300 python -u bench.py $A --steps 5 --warmup 1 --cpu-trials 16 --no-c3-strong > $OUT/cfg_$cfg.json 2> $OUT/cfg_$cfg.err || exit $?
+    timeout -k 10 300 python -u bench.py $A --full --steps 5 --warmup 1 --cpu-trials 16 --no-c3-strong > $OUT/cfg_$cfg.json 2> $OUT/cfg_$cfg.err || exit $?
   done
 fi
 echo done > $OUT/status.txt

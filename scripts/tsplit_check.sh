@@ -11,9 +11,9 @@ mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests/test_gpu_multirank.py -v -x --timeout 300 --timeout-method thread -p no:cacheprovider > $OUT/mr_tests.log 2>&1 || exit $?
 timeout -k 10 300 python -u scripts/shard_times.py C3 8 time > $OUT/shards_C3_time.log 2>&1 || exit $?
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus 2 --config C5 --dist-backend gloo --steps 2 --warmup 1 --bcast-chunks 4 \
+    --master-port 29533 bench.py --full --gpus 2 --config C5 --dist-backend gloo --steps 2 --warmup 1 --bcast-chunks 4 \
     > $OUT/mr_bench_c5_time.json 2> $OUT/mr_bench_c5_time.err || exit $?
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29534 bench.py --gpus 2 --config C5 --dist-backend gloo --steps 2 --warmup 1 --bcast-chunks 4 \
+    --master-port 29534 bench.py --full --gpus 2 --config C5 --dist-backend gloo --steps 2 --warmup 1 --bcast-chunks 4 \
     --decomposition dm > $OUT/mr_bench_c5_dm.json 2> $OUT/mr_bench_c5_dm.err || exit $?
 echo done
