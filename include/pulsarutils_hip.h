@@ -96,6 +96,20 @@ int pu_plan_create_ex(pu_plan **plan, int dtype, int acc, int64_t nchan, int64_t
                       const int64_t *shifts, int64_t ndm, const pu_plan_opts *opts);
 void pu_plan_destroy(pu_plan *plan);
 
+/* What pu_plan_create_ex would build for the same arguments, without building it: the same
+ * validation and the same planner run on the host alone (no device is touched, none is
+ * needed).  Fills up to ``ninfo`` fields of ``info`` in pu_plan_info's layout (the cert_*
+ * fields 0) and, if ``tables_digest`` is not NULL, a 64-bit digest of the tables the plan
+ * would upload, padding included: FNV-1a over each table's name, element count (uint64)
+ * and bytes, the tables taken in the order of their names (base, count, first, rec, rec8,
+ * recs, rowlen, slots, stages, tile_stages, tiles; a table the plan's mode does not use has
+ * count 0).  For tests of the planner (tests/test_plan_tables.py pins both against recorded
+ * values) and for developing planner changes away from a GPU.  No reference counterpart
+ * (the reference computes its shifts per trial, dedispersion.py:183-184). */
+int pu_plan_describe(int dtype, int acc, int64_t nchan, int64_t nsamples, const int64_t *shifts,
+                     int64_t ndm, const pu_plan_opts *opts, int64_t *info, int ninfo,
+                     uint64_t *tables_digest);
+
 /* Device scratch bytes pu_plan_search needs (per-tile partial statistics). */
 size_t pu_plan_workspace_bytes(const pu_plan *plan);
 

@@ -569,8 +569,9 @@ __device__ __forceinline__ void group_trials16(uint32_t (&lo)[C::D][2], const Re
     trials16_step<D, A, 0>(lo, w, rec, base);
 }
 
-// per 16-bit half: hi += lo >> 8, lo &= 255 (exact: lo < 2^16; hi counts 256s, < nchan < 2^16,
-// so neither 32-bit add carries across the halves)
+// per 16-bit half: hi += lo >> 8, lo &= 255 (exact: lo < 2^16; hi counts 256s of a sum of at
+// most nchan x 255 <= 2^24 - 1 - the planner's nchan <= 65793 check - so hi < 2^16 and
+// neither 32-bit add carries across the halves)
 template <int D>
 __device__ __forceinline__ void flush16(uint32_t (&lo)[D][2], uint32_t (&hi)[D][2])
 {
@@ -1036,7 +1037,7 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
         // the next slot's record is loaded a slot ahead (round 5: loaded on demand, its
         // scalar-load latency stood in front of every slot after a wave's first), through a
         // pointer stepped by W records: past the stage's last slot it reads the next stage's
-        // records or the table's padding (upload_sub: W records of zeros), never used.
+        // records or the table's padding (pad_slots: W records of zeros), never used.
         // Every slot has a first pass (len >= TT): peeled, with the tile's whole0.
         // Two slots per iteration with ping-pong records (rotating one record through a copy
         // cost a dozen scalar moves per slot).
@@ -1387,41 +1388,22 @@ int pick_variant(int dtype, int acc)
     }
 }
 
-// Host-side subband tables of a candidate plan (uploaded only for the plan that is kept).
-struct SubHost {
-    std::vector<i32x4> tiles, stages;
-    std::vector<i32x2> tile_stages;
-    std::vector<int32_t> slots, base;
-    std::vector<uint32_t> recs;
-};
-
-}  // namespace
-
-// Per-plan lock: a plan holds mutable per-call state (timing events and the launch
-// counter, the pinned certification copy and the last call's certification outcome),
-// and cached plans are shared across threads (ctypes releases the GIL).  Every entry
-// point that launches or reads that state holds it for the whole call.  Copying a plan
-// (reset_tables) keeps the destination's mutex.
-struct PlanLock {
-    std::mutex m;
-    PlanLock() = default;
-    PlanLock(const PlanLock &) {}
-    PlanLock &operator=(const PlanLock &) { return *this; }
-};
-
-struct pu_plan {
-    mutable PlanLock lock;
-    SubHost host;
+// The planner's input besides the shift table: the problem and the pu_plan_opts that reach
+// plan_sub (group, shape and LDS budget are arguments of the planning functions).
+struct PlanProblem {
     int dtype = 0, acc = 0, variant = 0;
     int64_t nchan = 0, n = 0, ndm = 0;
+    int opt_u8_dma = -1, opt_dt_major = -1, opt_slot16 = -1;
+};
+
+// Everything the planner produces (plan_channels, plan_sub, choose_plan): the geometry the
+// launch code reads and the host tables, which the kept plan uploads (DeviceTables) and
+// then releases - all but tile_first / tile_count.
+struct PlanTables {
     int K = 0, TT = 0;
     int ndt = 0, ntt = 0, ncc = 0, row_stride = 0, small_n = 0, max_spread = 0;
     size_t lds_bytes = 0;
-    int32_t *d_first = nullptr, *d_count = nullptr, *d_rowlen = nullptr, *d_base = nullptr;
-    u32x4 *d_rec = nullptr;
-    uint32_t *d_rec8 = nullptr;  // dedisp_f64_kernel's records (kF64Trials words per channel and wave)
-    // subband mode (group > 1): per tile {first, count, raw row length, copy bytes},
-    // stages {group begin, group end, item begin, item end}, build items, window records
+    // subband mode (group > 1)
     int group = 1, ngroups = 0, nslots_total = 0, raw_stride = 0, shape = SUB_WIDE;
     int dma8 = 0;  // subband plan stages 8-bit rows by LDS-DMA (rows must be 4-byte aligned)
     int slot16 = 0;  // subband plan with 16-bit integer slots (8-bit rows)
@@ -1429,14 +1411,127 @@ struct pu_plan {
     size_t slot_bytes = 0, zero_len = 0;
     int64_t exec_adds = 0, lds_traffic = 0;  // per launch (measurement: bench.py roofline)
     int64_t cost_windows16 = 0;  // 16-bit-slot windows per launch (the cost model's extra term)
-    std::vector<int32_t> tile_first, tile_count;  // DM tiles in launch order (pu_plan_dm_tiles)
     int64_t nstages = 0;
     int dt_major = 0;  // subband item order (SubArgs::dt_major)
-    int opt_u8_dma = -1, opt_dt_major = -1, opt_slot16 = -1;  // pu_plan_opts (planner inputs)
-    i32x4 *d_tiles = nullptr, *d_stages = nullptr;
-    i32x2 *d_tile_stages = nullptr;
-    int32_t *d_slots = nullptr;
-    uint32_t *d_recs = nullptr;
+    std::vector<int32_t> tile_first, tile_count;  // DM tiles in launch order (pu_plan_dm_tiles)
+    // channel mode: per tile first trial, trial count and row length; per (tile, channel) the
+    // row base (subband DMA mode: the DMA row words); window records (dedisp_kernel: rec,
+    // dedisp_f64_kernel: rec8, kF64Trials words per channel and wave + the first-window table)
+    std::vector<int32_t> first, count, rowlen, base;
+    std::vector<u32x4> rec;
+    std::vector<uint32_t> rec8;
+    // subband mode: per tile {first, count, raw row length, copy bytes} and {first stage,
+    // stage count}, stages {group begin, group end, item begin, item end}, build items
+    // (slot records), window records
+    std::vector<i32x4> tiles, stages;
+    std::vector<i32x2> tile_stages;
+    std::vector<int32_t> slots;
+    std::vector<uint32_t> recs;
+};
+
+// W (<= 16) records of padding after the slot records: the kernel's build loads each wave's
+// next slot record a slot ahead without clamping the index
+void pad_slots(PlanTables &t)
+{
+    if (t.group > 1) t.slots.resize(t.slots.size() + (size_t)16 * slot_stride(8), 0);
+}
+
+// FNV-1a (64 bits) over the tables as uploaded (pad_slots applied): each table's name,
+// element count and bytes, in the order of the names - not the upload's
+uint64_t digest_tables(const PlanTables &t)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto bytes = [&h](const void *p, size_t n) {
+        const unsigned char *b = static_cast<const unsigned char *>(p);
+        for (size_t i = 0; i < n; ++i) {
+            h ^= b[i];
+            h *= 0x100000001b3ull;
+        }
+    };
+    auto table = [&](const char *name, const auto &v) {
+        const uint64_t count = v.size();
+        bytes(name, strlen(name));
+        bytes(&count, sizeof count);
+        bytes(v.data(), v.size() * sizeof v[0]);
+    };
+    table("base", t.base);
+    table("count", t.count);
+    table("first", t.first);
+    table("rec", t.rec);
+    table("rec8", t.rec8);
+    table("recs", t.recs);
+    table("rowlen", t.rowlen);
+    table("slots", t.slots);
+    table("stages", t.stages);
+    table("tile_stages", t.tile_stages);
+    table("tiles", t.tiles);
+    return h;
+}
+
+// An owning device pointer (move-only): the one place a plan table is freed.
+template <typename T>
+struct DevicePtr {
+    T *ptr = nullptr;
+    DevicePtr() = default;
+    DevicePtr(DevicePtr &&o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+    DevicePtr &operator=(DevicePtr &&o) noexcept
+    {
+        std::swap(ptr, o.ptr);
+        return *this;
+    }
+    ~DevicePtr() { (void)hipFree(ptr); }
+    operator T *() const { return ptr; }
+};
+
+// The plan's tables in device memory.
+struct DeviceTables {
+    DevicePtr<int32_t> first, count, rowlen, base, slots;
+    DevicePtr<u32x4> rec;
+    DevicePtr<uint32_t> rec8, recs;
+    DevicePtr<i32x4> tiles, stages;
+    DevicePtr<i32x2> tile_stages;
+
+    // Uploads every table the plan's mode fills, the padded slot records included, and
+    // releases each host copy.
+    int upload(PlanTables &t)
+    {
+        pad_slots(t);
+        int rc = PU_OK;
+        auto put = [&rc](auto &dst, auto &vec) {
+            if (rc || vec.empty()) return;
+            const size_t bytes = vec.size() * sizeof vec[0];
+            rc = pu::hip_check(hipMalloc((void **)&dst.ptr, std::max<size_t>(bytes, 16)), "hipMalloc(plan)");
+            if (rc) return;
+            rc = pu::hip_check(hipMemcpy(dst.ptr, vec.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(plan)");
+            std::remove_reference_t<decltype(vec)>().swap(vec);
+        };
+        put(first, t.first);
+        put(count, t.count);
+        put(rowlen, t.rowlen);
+        put(tiles, t.tiles);
+        put(tile_stages, t.tile_stages);
+        put(stages, t.stages);
+        put(slots, t.slots);
+        put(recs, t.recs);
+        put(base, t.base);
+        put(rec, t.rec);
+        put(rec8, t.rec8);
+        return rc;
+    }
+};
+
+}  // namespace
+
+// A plan: the problem, what the planner made of it, the device tables and the per-call
+// state (timing events and the launch counter, the pinned certification copy and the last
+// call's certification outcome).  Cached plans are shared across threads (ctypes releases
+// the GIL): every entry point that launches or reads the per-call state holds the lock
+// for the whole call.
+struct pu_plan {
+    mutable std::mutex lock;
+    PlanProblem pb;
+    PlanTables t;
+    DeviceTables d;
     // optional kernel timing: events before the first and after the last launch of
     // each dispatch
     std::vector<hipEvent_t> ev_start, ev_stop;
@@ -1464,9 +1559,9 @@ int ensure_lds(Kern kern, size_t bytes)
 int launch_f64(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s, bool tin_f32)
 {
     // records, then the first-window table (planner: one upload)
-    const uint32_t *first_off = p->d_rec8 + (size_t)p->ndt * p->nchan * kTPT / 2;
-    return pu_dd_launch_f64(tin_f32, plane, &a, sizeof a, p->lds_bytes, p->d_first, p->d_count, p->d_rowlen,
-                            p->d_base, p->d_rec8, first_off, s, kF64Waves);
+    const uint32_t *first_off = p->d.rec8 + (size_t)p->t.ndt * p->pb.nchan * kTPT / 2;
+    return pu_dd_launch_f64(tin_f32, plane, &a, sizeof a, p->t.lds_bytes, p->d.first, p->d.count, p->d.rowlen,
+                            p->d.base, p->d.rec8, first_off, s, kF64Waves);
 }
 
 template <typename Tin, typename Tl, typename Ta>
@@ -1475,23 +1570,23 @@ int launch_variant(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_
     const dim3 grid((unsigned)((int64_t)a.ndt * a.ntt_run)), block(kThreads);
     if (plane) {
         auto kern = dedisp_kernel<Tin, Tl, Ta, true, false>;
-        int rc = ensure_lds(kern, p->lds_bytes);
+        int rc = ensure_lds(kern, p->t.lds_bytes);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, grid, block, p->lds_bytes, s, a, p->d_first, p->d_count, p->d_rowlen, p->d_base,
-                           p->d_rec);
+        hipLaunchKernelGGL(kern, grid, block, p->t.lds_bytes, s, a, p->d.first, p->d.count, p->d.rowlen, p->d.base,
+                           p->d.rec);
     } else {
         auto kern = dedisp_kernel<Tin, Tl, Ta, false, true>;
-        int rc = ensure_lds(kern, p->lds_bytes);
+        int rc = ensure_lds(kern, p->t.lds_bytes);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, grid, block, p->lds_bytes, s, a, p->d_first, p->d_count, p->d_rowlen, p->d_base,
-                           p->d_rec);
+        hipLaunchKernelGGL(kern, grid, block, p->t.lds_bytes, s, a, p->d.first, p->d.count, p->d.rowlen, p->d.base,
+                           p->d.rec);
     }
     return pu::launch_check("dedisp_kernel");
 }
 
 int dispatch_variant(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 {
-    switch (p->variant) {
+    switch (p->pb.variant) {
     case V_U8_F32: return launch_variant<uint8_t, float, float>(p, a, plane, s);
     case V_F32_F32: return launch_variant<float, float, float>(p, a, plane, s);
     case V_F64_F64: return launch_f64(p, a, plane, s, false);
@@ -1508,10 +1603,10 @@ int launch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 {
     SubArgs sa{};
     sa.o = a;
-    sa.ngroups = p->ngroups;
-    sa.raw_stride = p->raw_stride;
-    sa.zero_len = (int32_t)p->zero_len;
-    sa.lds_bytes = (int32_t)p->lds_bytes;
+    sa.ngroups = p->t.ngroups;
+    sa.raw_stride = p->t.raw_stride;
+    sa.zero_len = (int32_t)p->t.zero_len;
+    sa.lds_bytes = (int32_t)p->t.lds_bytes;
     sa.stamps = p->d_stamps;
     sa.dma_waves = std::min<int>(8, C::W);  // C2 17.6 vs 18.95 ms with all 16 waves, C3 141 vs 150 (625 trials)
 #ifdef PU_STAMPS
@@ -1522,24 +1617,24 @@ int launch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 
     const int64_t nitems = (int64_t)a.ndt * a.ntt_run;
     sa.nitems = (int32_t)nitems;
-    sa.base_bits = p->base_bits;
-    sa.dt_major = p->dt_major;
+    sa.base_bits = p->t.base_bits;
+    sa.dt_major = p->t.dt_major;
     const int64_t nblk = nitems;
     const dim3 grid((unsigned)nblk), block(C::THREADS);
     auto go = [&](auto kern) {
-        int rc = ensure_lds(kern, p->lds_bytes);
+        int rc = ensure_lds(kern, p->t.lds_bytes);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, grid, block, p->lds_bytes, s, sa, p->d_tiles, p->d_tile_stages, p->d_stages,
-                           p->d_slots, p->d_base, p->d_recs);
+        hipLaunchKernelGGL(kern, grid, block, p->t.lds_bytes, s, sa, p->d.tiles, p->d.tile_stages, p->d.stages,
+                           p->d.slots, p->d.base, p->d.recs);
         return pu::launch_check("dedisp_sub_kernel");
     };
     if constexpr (std::is_same<Tin, uint8_t>::value) {
         if constexpr (C::K == 4) {
-            if (p->slot16)
+            if (p->t.slot16)
                 return plane ? go(dedisp_sub_kernel<C, Tin, G, true, false, true, true>)
                              : go(dedisp_sub_kernel<C, Tin, G, false, true, true, true>);
         }
-        if (p->dma8)
+        if (p->t.dma8)
             return plane ? go(dedisp_sub_kernel<C, Tin, G, true, false, true>)
                          : go(dedisp_sub_kernel<C, Tin, G, false, true, true>);
     }
@@ -1550,24 +1645,24 @@ int launch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 template <class C, typename Tin>
 int launch_sub_g(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 {
-    switch (p->group) {
+    switch (p->t.group) {
     case 2: return launch_sub<C, Tin, 2>(p, a, plane, s);
     case 4: return launch_sub<C, Tin, 4>(p, a, plane, s);
     case 8: return launch_sub<C, Tin, 8>(p, a, plane, s);
     }
-    pu::set_error("bad plan group %d", p->group);
+    pu::set_error("bad plan group %d", p->t.group);
     return PU_EINVAL;
 }
 
 template <typename Tin>
 int launch_sub_shape(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 {
-    return with_shape(p->shape, [&](auto c) { return launch_sub_g<decltype(c), Tin>(p, a, plane, s); });
+    return with_shape(p->t.shape, [&](auto c) { return launch_sub_g<decltype(c), Tin>(p, a, plane, s); });
 }
 
 int dispatch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 {
-    switch (p->dtype) {
+    switch (p->pb.dtype) {
     case PU_U8: return launch_sub_shape<uint8_t>(p, a, plane, s);
     case PU_F32: return launch_sub_shape<float>(p, a, plane, s);
     case PU_F64: return launch_sub_shape<double>(p, a, plane, s);
@@ -1581,7 +1676,7 @@ int dispatch(pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
     const size_t nslot = p->ev_start.size();
     const size_t slot = nslot ? (size_t)(p->launches % (int64_t)nslot) : 0;
     if (nslot) PU_TRY_HIP(hipEventRecord(p->ev_start[slot], s));
-    int rc = p->group > 1 ? dispatch_sub(p, a, plane, s) : dispatch_variant(p, a, plane, s);
+    int rc = p->t.group > 1 ? dispatch_sub(p, a, plane, s) : dispatch_variant(p, a, plane, s);
     if (rc) return rc;
     if (nslot) PU_TRY_HIP(hipEventRecord(p->ev_stop[slot], s));
     ++p->launches;
@@ -1600,38 +1695,26 @@ void free_plan(pu_plan *p)
 {
     if (!p) return;
     destroy_events(p);
-    (void)hipFree(p->d_first);
-    (void)hipFree(p->d_count);
-    (void)hipFree(p->d_rowlen);
-    (void)hipFree(p->d_base);
-    (void)hipFree(p->d_rec);
-    (void)hipFree(p->d_rec8);
-    (void)hipFree(p->d_tiles);
-    (void)hipFree(p->d_tile_stages);
-    (void)hipFree(p->d_stages);
-    (void)hipFree(p->d_slots);
-    (void)hipFree(p->d_recs);
     (void)hipFree(p->d_stamps);
     if (p->h_cert) (void)hipHostFree(p->h_cert);
-    delete p;
+    delete p;  // the device tables: ~DeviceTables
 }
 
-template <typename T>
-int upload(T **dst, const std::vector<T> &vec)
-{
-    const size_t bytes = vec.size() * sizeof(T);
-    int rc = pu::hip_check(hipMalloc((void **)dst, std::max<size_t>(bytes, 16)), "hipMalloc(plan)");
-    if (rc) return rc;
-    return pu::hip_check(hipMemcpy(*dst, vec.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(plan)");
-}
+// ---- The planner: plan_channels, plan_sub and choose_plan are host arithmetic from
+// (problem, shifts, options) to a PlanTables value; no device is touched (pu_plan_describe
+// runs them on a machine without one).
 
 // ---- channel mode (every variant): DM tiles of <= kTPT trials with per-channel shift
 // spread <= kMaxSpread; per (tile, channel) the modular row base; u16 window records.
-int plan_channels(pu_plan *p, const int64_t *shifts, size_t budget)
+int plan_channels(const PlanProblem &pb, const int64_t *shifts, size_t budget, PlanTables &out)
 {
-    const int64_t nchan = p->nchan, n = p->n, ndm = p->ndm;
-    const int esz = kVariants[p->variant].lds_elem;
+    const int64_t nchan = pb.nchan, n = pb.n, ndm = pb.ndm;
+    const int esz = kVariants[pb.variant].lds_elem;
     const int E = 8 / esz;
+    out = PlanTables{};
+    out.K = E * (kVariants[pb.variant].acc_f64 && esz == 4 ? 2 : 4);  // dedisp_kernel's J
+    out.TT = 64 * out.K;
+    out.ntt = (int)((n + out.TT - 1) / out.TT);
     std::vector<int32_t> first, count;
     {
         std::vector<int64_t> mn((size_t)nchan), mx((size_t)nchan);
@@ -1711,33 +1794,33 @@ int plan_channels(pu_plan *p, const int64_t *shifts, size_t budget)
             spread = std::max(spread, (int)std::min<int64_t>(m1 - m0, n - 1));
         }
         max_spread = std::max(max_spread, spread);
-        rowlen[t] = p->TT + spread;
+        rowlen[t] = out.TT + spread;
         max_rowlen = std::max(max_rowlen, rowlen[t]);
     }
     const int epp = 256 / esz;
-    const bool fsm = kVariants[p->variant].fsm != 0;
-    p->row_stride = (max_rowlen + E + epp - 1) / epp * epp;
-    p->small_n = (int64_t)p->row_stride + 2 > n ? 1 : 0;
-    const int nbuf = kVariants[p->variant].dma ? 2 : 1;
-    const int64_t chan_bytes = (int64_t)E * p->row_stride * esz;
+    const bool fsm = kVariants[pb.variant].fsm != 0;
+    out.row_stride = (max_rowlen + E + epp - 1) / epp * epp;
+    out.small_n = (int64_t)out.row_stride + 2 > n ? 1 : 0;
+    const int nbuf = kVariants[pb.variant].dma ? 2 : 1;
+    const int64_t chan_bytes = (int64_t)E * out.row_stride * esz;
     if (chan_bytes > 32768) {
-        pu::set_error("pu_plan_create: LDS row of %d elements does not fit", p->row_stride);
+        pu::set_error("pu_plan_create: LDS row of %d elements does not fit", out.row_stride);
         return PU_EUNSUPPORTED;
     }
-    p->ndt = ndt;
-    p->max_spread = max_spread;
+    out.ndt = ndt;
+    out.max_spread = max_spread;
     // dedisp_f64_kernel: two float64 row buffers, plus one raw float32 row per channel for
     // float32 inputs (whole 256-byte DMA pieces)
     // (its stride: the row_stride's, as the kernel computes it), and two slots of window
     // records (one 256-byte DMA per channel, + 2 channels of read-ahead each)
-    const int64_t raw_bytes = fsm && p->dtype == PU_F32 ? ((int64_t)p->row_stride * 4 + 255) / 256 * 256 : 0;
+    const int64_t raw_bytes = fsm && pb.dtype == PU_F32 ? ((int64_t)out.row_stride * 4 + 255) / 256 * 256 : 0;
     constexpr int64_t kRecChan = 2 * kTPT;  // u16 words
     const int64_t per_chan = nbuf * chan_bytes + raw_bytes + (fsm ? 2 * kRecChan : 0);
     const int64_t fixed = fsm ? 2 * 2 * kRecChan : 0;
-    p->ncc = (int)std::max<int64_t>(1, std::min<int64_t>(nchan, (int64_t)((budget - fixed) / per_chan)));
-    p->lds_bytes = (size_t)p->ncc * per_chan + fixed;
-    if (p->lds_bytes > 160 * 1024) {
-        pu::set_error("pu_plan_create: LDS row of %d elements does not fit", p->row_stride);
+    out.ncc = (int)std::max<int64_t>(1, std::min<int64_t>(nchan, (int64_t)((budget - fixed) / per_chan)));
+    out.lds_bytes = (size_t)out.ncc * per_chan + fixed;
+    if (out.lds_bytes > 160 * 1024) {
+        pu::set_error("pu_plan_create: LDS row of %d elements does not fit", out.row_stride);
         return PU_EUNSUPPORTED;
     }
     // window records: per (tile, channel, wave) 8 x u16 = LDS byte offset of each
@@ -1752,12 +1835,12 @@ int plan_channels(pu_plan *p, const int64_t *shifts, size_t budget)
     // predecessor's window) so that each pair starts and ends in the kernel's state 0.
     // After the records: per (tile, channel, wave) the byte offset of the channel's first
     // window (read at chunk starts).
-    const size_t copy_bytes = (size_t)p->row_stride * esz;
+    const size_t copy_bytes = (size_t)out.row_stride * esz;
     std::vector<u32x4> rec(fsm ? 0 : (size_t)ndt * nchan * kWaves);
     std::vector<uint32_t> rec8(fsm ? (size_t)ndt * nchan * kTPT / 2 + (size_t)ndt * nchan * kF64Waves : 0);
     int64_t f64_reads = 0;  // window reads of dedisp_f64_kernel, per launch and time tile
     if (fsm) {
-        if (p->ncc * chan_bytes / 8 + 1 >= (int64_t(1) << 16)) {
+        if (out.ncc * chan_bytes / 8 + 1 >= (int64_t(1) << 16)) {
             pu::set_error("pu_plan_create: float64 window records overflow");
             return PU_EUNSUPPORTED;
         }
@@ -1782,9 +1865,9 @@ int plan_channels(pu_plan *p, const int64_t *shifts, size_t budget)
         };
         auto emit = [&](size_t t, int64_t c, int w, const bool (&re)[FD]) {
             const int32_t *rr = rel.data() + (t * nchan + c) * kTPT + w * FD;
-            const uint32_t cb = (uint32_t)((c % p->ncc) * chan_bytes);
+            const uint32_t cb = (uint32_t)((c % out.ncc) * chan_bytes);
             first8[(t * nchan + c) * kF64Waves + w] = cb + 8u * (uint32_t)rr[0];
-            const bool nxt_ok = c + 1 < nchan && (c + 1) % p->ncc != 0;
+            const bool nxt_ok = c + 1 < nchan && (c + 1) % out.ncc != 0;
             const uint32_t nxt_off =
                 nxt_ok ? (uint32_t)(cb + chan_bytes + 8u * (uint32_t)rel[((t * nchan + c + 1) * kTPT) + w * FD]) : 0u;
             uint32_t *r = rec8.data() + ((t * nchan + c) * kF64Waves + w) * (FD / 2);
@@ -1801,8 +1884,8 @@ int plan_channels(pu_plan *p, const int64_t *shifts, size_t budget)
         // count is odd): a pair's reload count - a lone channel's - is made even, so every
         // pair starts and ends in state 0 (the pair's second channel has an entry for each)
         for (size_t t = 0; t < (size_t)ndt; ++t)
-            for (int64_t c0 = 0; c0 < nchan; c0 += p->ncc) {
-                const int64_t nc = std::min<int64_t>(p->ncc, nchan - c0);
+            for (int64_t c0 = 0; c0 < nchan; c0 += out.ncc) {
+                const int64_t nc = std::min<int64_t>(out.ncc, nchan - c0);
                 for (int64_t ci = 0; ci < nc; ci += 2)
                     for (int w = 0; w < kF64Waves; ++w) {
                         bool ra[FD], rb[FD];
@@ -1837,22 +1920,22 @@ int plan_channels(pu_plan *p, const int64_t *shifts, size_t budget)
                 for (int u = 0; u < 4; ++u) r[u] = words[2 * u] | (words[2 * u + 1] << 16);
                 rec[(t * nchan + c) * kWaves + w] = r;
             }
-    if ((int64_t)p->ndt * p->ntt >= (int64_t(1) << 31)) {
+    if ((int64_t)out.ndt * out.ntt >= (int64_t(1) << 31)) {
         pu::set_error("pu_plan_create: grid too large");
         return PU_EINVAL;
     }
-    p->exec_adds = ndm * nchan * (int64_t)p->ntt * p->TT;
+    out.exec_adds = ndm * nchan * (int64_t)out.ntt * out.TT;
     // LDS bytes per launch (bench.py roofline): per time tile, the staged rows (E copies of
     // row_stride elements per channel) and, per active wave and channel, one J x 8-byte
     // x 64-lane window read for the first trial and for every trial whose window differs
-    // from the previous trial's (the reload flag); J = p->K / E reads per window
+    // from the previous trial's (the reload flag); J = out.K / E reads per window
     {
-        const int J = p->K / E;
+        const int J = out.K / E;
         int64_t lds_tile = 0;
         for (size_t t = 0; t < (size_t)ndt; ++t) {
             // staged rows (dedisp_f64_kernel on float32: + the raw row's DMA write and the
             // converting pass's read)
-            lds_tile += nchan * (int64_t)E * p->row_stride * esz + (raw_bytes ? nchan * 2 * raw_bytes : 0);
+            lds_tile += nchan * (int64_t)E * out.row_stride * esz + (raw_bytes ? nchan * 2 * raw_bytes : 0);
             if (fsm) continue;  // the float64 kernel's reads: f64_reads (records, below)
             for (int w = 0; w < kWaves && w * kD < count[t]; ++w)
                 for (int64_t c = 0; c < nchan; ++c) {
@@ -1863,17 +1946,17 @@ int plan_channels(pu_plan *p, const int64_t *shifts, size_t budget)
                 }
         }
         lds_tile += f64_reads * J * 64 * 8;
-        p->lds_traffic = lds_tile * p->ntt;
+        out.lds_traffic = lds_tile * out.ntt;
     }
-    p->tile_first = first;
-    p->tile_count = count;
-    int rc = PU_OK;
-    if (!rc) rc = upload(&p->d_first, first);
-    if (!rc) rc = upload(&p->d_count, count);
-    if (!rc) rc = upload(&p->d_rowlen, rowlen);
-    if (!rc) rc = upload(&p->d_base, base);
-    if (!rc) rc = fsm ? upload(&p->d_rec8, rec8) : upload(&p->d_rec, rec);
-    return rc;
+    out.tile_first = first;
+    out.tile_count = count;
+    out.first = std::move(first);
+    out.count = std::move(count);
+    out.rowlen = std::move(rowlen);
+    out.base = std::move(base);
+    out.rec = std::move(rec);
+    out.rec8 = std::move(rec8);
+    return PU_OK;
 }
 
 // ---- subband mode planning (float32 accumulation).  Returns PU_EUNSUPPORTED when one
@@ -1889,9 +1972,10 @@ struct SubSlot {
     int64_t d0;      // one trial with this vector
 };
 
-int plan_sub(pu_plan *p, const int64_t *shifts, int G, int shape, size_t budget)
+// Fills ``out`` only on success.
+int plan_sub(const PlanProblem &pb, const int64_t *shifts, int G, int shape, size_t budget, PlanTables &out)
 {
-    const int64_t nchan = p->nchan, n = p->n, ndm = p->ndm;
+    const int64_t nchan = pb.nchan, n = pb.n, ndm = pb.ndm;
     const int W = with_shape(shape, [](auto c) { return decltype(c)::W; });
     const int D = with_shape(shape, [](auto c) { return decltype(c)::D; });
     const int64_t TT = with_shape(shape, [](auto c) { return (int64_t)decltype(c)::TT; });
@@ -1899,17 +1983,22 @@ int plan_sub(pu_plan *p, const int64_t *shifts, int G, int shape, size_t budget)
     const int ngroups = (int)((nchan + G - 1) / G);
     // 8-bit rows are staged as bytes by LDS-DMA when every row window starts on a dword
     // (n % 4 == 0; the row's misalignment base % 4 is folded into the slot sources)
-    bool dma8 = p->dtype == PU_U8 && n % 4 == 0;
-    dma8 = dma8 && pu::knob("PU_U8_DMA", p->opt_u8_dma) != 0;
-    const bool dma = p->dtype == PU_F32 || dma8;
+    bool dma8 = pb.dtype == PU_U8 && n % 4 == 0;
+    dma8 = dma8 && pu::knob("PU_U8_DMA", pb.opt_u8_dma) != 0;
+    const bool dma = pb.dtype == PU_F32 || dma8;
     const int64_t eb = dma8 ? 1 : 4;  // bytes per staged raw element
     // 16-bit integer slots: 8-bit DMA rows in 256-sample time tiles; four
     // alignment copies of >= 384 u16 elements, slots of <= 512 elements (span <= kS16Span)
     // Every G: with the four-per-lane build G = 8 is faster with 16-bit slots too (C3 625
     // trials 113.5 vs 114.3 ms, 5000: 936 vs 957 - DESIGN.md §4.1b, profiles/r06/experiments/
     // slot16/); the per-window cost term below makes the planner pick G per grid
-    const int s16opt = pu::knob("PU_SLOT16", p->opt_slot16);  // -1 auto (= on), 0 off, 1 on
+    const int s16opt = pu::knob("PU_SLOT16", pb.opt_slot16);  // -1 auto (= on), 0 off, 1 on
     const bool s16 = dma8 && TT == 256 && s16opt != 0;
+    // flush16's carry-free halves: a series sums to at most nchan x 255 <= 2^24 - 1
+    if (s16 && nchan * 255 > (int64_t(1) << 24) - 1) {
+        pu::set_error("pu_plan_create: 16-bit slots exact only for nchan <= 65793");
+        return PU_EINVAL;
+    }
     const int64_t ncopies = s16 ? 4 : 2;
     const bool pack_cover = n < (int64_t(1) << 24);  // row bases fit 24 bits: covers above them
     // a stage's raw rows (DMA mode) and its slots share the LDS budget; a stage holds
@@ -2061,7 +2150,7 @@ int plan_sub(pu_plan *p, const int64_t *shifts, int G, int shape, size_t budget)
     // span sized every slot before): more groups per stage
     // 16-bit slots by their own span; float32 slots by theirs rounded up to whole build passes
     // of 64 U elements (sub_item's U), at most the tile's size (sub_item's copy_bytes_of)
-    const int64_t UP64 = 64 * std::min<int64_t>((TT + 80 + 63) / 64, (p->dtype == PU_F64 ? 20 : 40) / G);
+    const int64_t UP64 = 64 * std::min<int64_t>((TT + 80 + 63) / 64, (pb.dtype == PU_F64 ? 20 : 40) / G);
     auto slot_copy = [&](size_t t, const SubSlot &sl) {
         if (s16) return copy_of(sl.hi - sl.lo);
         const int64_t whole = (TT + (sl.hi - sl.lo) + 2 + UP64 - 1) / UP64 * UP64 * 4;
@@ -2208,7 +2297,7 @@ int plan_sub(pu_plan *p, const int64_t *shifts, int G, int shape, size_t budget)
     // for the time-tile-major order too cost C3 1.1 % - 1109 vs 1122 ms.)
     const int64_t ntt_plan = (n + TT - 1) / TT;
     bool dt_major = (int64_t)ndt * ntt_plan < kDtMajorItems;
-    if (p->opt_dt_major >= 0) dt_major = p->opt_dt_major != 0;
+    if (pb.opt_dt_major >= 0) dt_major = pb.opt_dt_major != 0;
     dt_major = pu::knob("PU_DT_MAJOR", dt_major ? 1 : 0) != 0;
     if (dt_major) {
         std::vector<int> perm((size_t)ndt);
@@ -2242,117 +2331,69 @@ int plan_sub(pu_plan *p, const int64_t *shifts, int G, int shape, size_t budget)
         pu::set_error("pu_plan_create: grid too large");
         return PU_EINVAL;
     }
-    p->group = G;
-    p->ngroups = ngroups;
-    p->ndt = ndt;
-    p->shape = shape;
-    p->K = (int)(TT / 64);
-    p->TT = (int)TT;
-    p->ntt = (int)ntt;
-    p->ncc = (int)max_stage_chans;
-    p->raw_stride = (int)raw_stride;
-    p->row_stride = (int)raw_stride;
-    p->max_spread = (int)max_spread;
-    p->small_n = raw_stride + 2 > n ? 1 : 0;
-    p->zero_len = zr ? (size_t)(((raw_stride + 64) * eb + 3) / 4) : 0;  // floats
-    p->dma8 = dma8 ? 1 : 0;
-    p->slot16 = s16 ? 1 : 0;
-    p->base_bits = pack_cover ? 24 : 31;
-    p->slot_bytes = (size_t)slot_used;
-    p->lds_bytes = (size_t)lds_total;
-    p->nslots_total = (int)(slotmeta.size() / ms);
-    p->nstages = (int64_t)stages.size();
-    p->dt_major = dt_major ? 1 : 0;
-    p->exec_adds = adds_tile * ntt;
-    p->lds_traffic = lds_tile * ntt;
-    p->cost_windows16 = win16_tile * ntt;
-    // host tables only: the caller uploads the plan it keeps (upload_sub), so comparing
-    // candidate group sizes costs no device memory
-    p->tile_first.resize((size_t)ndt);
-    p->tile_count.resize((size_t)ndt);
+    out = PlanTables{};
+    out.group = G;
+    out.ngroups = ngroups;
+    out.ndt = ndt;
+    out.shape = shape;
+    out.K = (int)(TT / 64);
+    out.TT = (int)TT;
+    out.ntt = (int)ntt;
+    out.ncc = (int)max_stage_chans;
+    out.raw_stride = (int)raw_stride;
+    out.row_stride = (int)raw_stride;
+    out.max_spread = (int)max_spread;
+    out.small_n = raw_stride + 2 > n ? 1 : 0;
+    out.zero_len = zr ? (size_t)(((raw_stride + 64) * eb + 3) / 4) : 0;  // floats
+    out.dma8 = dma8 ? 1 : 0;
+    out.slot16 = s16 ? 1 : 0;
+    out.base_bits = pack_cover ? 24 : 31;
+    out.slot_bytes = (size_t)slot_used;
+    out.lds_bytes = (size_t)lds_total;
+    out.nslots_total = (int)(slotmeta.size() / ms);
+    out.nstages = (int64_t)stages.size();
+    out.dt_major = dt_major ? 1 : 0;
+    out.exec_adds = adds_tile * ntt;
+    out.lds_traffic = lds_tile * ntt;
+    out.cost_windows16 = win16_tile * ntt;
+    out.tile_first.resize((size_t)ndt);
+    out.tile_count.resize((size_t)ndt);
     for (int t = 0; t < ndt; ++t) {
-        p->tile_first[t] = tiles[t].x;
-        p->tile_count[t] = tiles[t].y;
+        out.tile_first[t] = tiles[t].x;
+        out.tile_count[t] = tiles[t].y;
     }
-    SubHost &h = p->host;
-    h.tiles = std::move(tiles);
-    h.tile_stages = std::move(tile_stages);
-    h.stages = std::move(stages);
-    h.slots = std::move(slotmeta);
-    h.recs = std::move(rec);
-    h.base = dma ? std::move(base) : std::vector<int32_t>();
+    out.tiles = std::move(tiles);
+    out.tile_stages = std::move(tile_stages);
+    out.stages = std::move(stages);
+    out.slots = std::move(slotmeta);
+    out.recs = std::move(rec);
+    if (dma) out.base = std::move(base);
     return PU_OK;
-}
-
-int upload_sub(pu_plan *p)
-{
-    SubHost &h = p->host;
-    int rc = PU_OK;
-    if (!rc) rc = upload(&p->d_tiles, h.tiles);
-    if (!rc) rc = upload(&p->d_tile_stages, h.tile_stages);
-    if (!rc) rc = upload(&p->d_stages, h.stages);
-    // W (<= 16) records of padding: the kernel's build loads each wave's next slot record a
-    // slot ahead without clamping the index
-    h.slots.resize(h.slots.size() + (size_t)16 * slot_stride(8), 0);
-    if (!rc) rc = upload(&p->d_slots, h.slots);
-    if (!rc) rc = upload(&p->d_recs, h.recs);
-    if (!rc && !h.base.empty()) rc = upload(&p->d_base, h.base);
-    h = SubHost{};
-    return rc;
-}
-
-void reset_tables(pu_plan *p)
-{
-    pu_plan keep;
-    keep.dtype = p->dtype;
-    keep.acc = p->acc;
-    keep.variant = p->variant;
-    keep.nchan = p->nchan;
-    keep.n = p->n;
-    keep.ndm = p->ndm;
-    keep.K = p->K;
-    keep.TT = p->TT;
-    keep.ntt = p->ntt;
-    keep.opt_u8_dma = p->opt_u8_dma;
-    keep.opt_slot16 = p->opt_slot16;
-    keep.opt_dt_major = p->opt_dt_major;
-    (void)hipFree(p->d_first);
-    (void)hipFree(p->d_count);
-    (void)hipFree(p->d_rowlen);
-    (void)hipFree(p->d_base);
-    (void)hipFree(p->d_rec);
-    (void)hipFree(p->d_rec8);
-    (void)hipFree(p->d_tiles);
-    (void)hipFree(p->d_tile_stages);
-    (void)hipFree(p->d_stages);
-    (void)hipFree(p->d_slots);
-    (void)hipFree(p->d_recs);
-    *p = keep;
 }
 
 // The plan keeps its shift table (host) for the exact recomputation of flagged trials,
 // and a pinned copy of the certification state.
 int finish_plan(pu_plan *p, const int64_t *shifts)
 {
-    p->shifts.assign(shifts, shifts + p->ndm * p->nchan);
+    p->shifts.assign(shifts, shifts + p->pb.ndm * p->pb.nchan);
     return pu::hip_check(hipHostMalloc((void **)&p->h_cert, sizeof(CertState), hipHostMallocDefault),
                          "hipHostMalloc(cert)");
 }
 
 // partial records in the plan's accumulation type (the epilogues' sums are float32
 // for float32 accumulation: a float record stores them exactly)
-size_t part_elem(const pu_plan *p) { return kVariants[p->variant].acc_f64 ? sizeof(double) : sizeof(float); }
-size_t part_bytes(const pu_plan *p) { return ((size_t)p->ndm * p->ntt * kPartStride * part_elem(p) + 255) & ~size_t(255); }
+size_t part_elem(const PlanProblem &pb) { return kVariants[pb.variant].acc_f64 ? sizeof(double) : sizeof(float); }
+size_t part_bytes(const pu_plan *p) { return ((size_t)p->pb.ndm * p->t.ntt * kPartStride * part_elem(p->pb) + 255) & ~size_t(255); }
 
 // Rounding model of the plan's fast statistics (pu_finalize_kernel).
 CertModel cert_model(const pu_plan *p)
 {
     CertModel m{};
-    if (kVariants[p->variant].acc_f64) {
+    if (kVariants[p->pb.variant].acc_f64) {
         m.tie_check = 1;  // float64 channel order: the reference's series bit for bit
         m.e_rel = 0x1p-50;
         m.gamma = 0x1p-44;
-    } else if (p->dtype == PU_U8 && 8 * 255 * p->nchan < (int64_t(1) << 24)) {
+    } else if (p->pb.dtype == PU_U8 && 8 * 255 * p->pb.nchan < (int64_t(1) << 24)) {
         // integer sums (and their 8-sample rebins) below 2^24: exact in float32.  The
         // epilogue's sums of squares: <= 14 float32 roundings of nonnegative terms (the
         // shifted value, the square-and-add, 4 lane-local adds, the pair add, 2 permlane
@@ -2365,7 +2406,7 @@ CertModel cert_model(const pu_plan *p)
         // with an 8x margin, relative to the series' magnitude; S/N ties within the
         // float32 tolerance are not recomputed (the stated tolerance covers them)
         m.tie_check = 0;
-        m.e_rel = 8.0 * 0x1p-24 * std::sqrt((double)p->nchan);
+        m.e_rel = 8.0 * 0x1p-24 * std::sqrt((double)p->pb.nchan);
         m.gamma = 0x1p-19;
     }
     return m;
@@ -2379,15 +2420,15 @@ int launch_finalize(pu_plan *p, const void *part, double *mx, double *sd, double
     CertState *cert = reinterpret_cast<CertState *>(ws + part_bytes(p));
     int32_t *list = reinterpret_cast<int32_t *>(cert + 1);
     if (!cleared) PU_TRY_HIP(hipMemsetAsync(cert, 0, sizeof(CertState), s));
-    if (count < 0) count = p->ndm - first;
+    if (count < 0) count = p->pb.ndm - first;
     if (count == 0) return PU_OK;
-    if (part_elem(p) == sizeof(float))
+    if (part_elem(p->pb) == sizeof(float))
         hipLaunchKernelGGL(pu_finalize_kernel<float>, dim3((unsigned)count), dim3(256), 0, s,
-                           reinterpret_cast<const float *>(part), p->ntt, (int)p->n, p->TT, mx, sd, snr, win, cert_model(p),
+                           reinterpret_cast<const float *>(part), p->t.ntt, (int)p->pb.n, p->t.TT, mx, sd, snr, win, cert_model(p),
                            cert, list, (int)first);
     else
         hipLaunchKernelGGL(pu_finalize_kernel<double>, dim3((unsigned)count), dim3(256), 0, s,
-                           reinterpret_cast<const double *>(part), p->ntt, (int)p->n, p->TT, mx, sd, snr, win, cert_model(p),
+                           reinterpret_cast<const double *>(part), p->t.ntt, (int)p->pb.n, p->t.TT, mx, sd, snr, win, cert_model(p),
                            cert, list, (int)first);
     return pu::launch_check("pu_finalize_kernel");
 }
@@ -2402,7 +2443,7 @@ int launch_finalize(pu_plan *p, const void *part, double *mx, double *sd, double
 int resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, double *sd, double *snr, int32_t *win,
                     char *ws, hipStream_t s, int64_t first = 0, int64_t count = -1)
 {
-    if (count < 0) count = p->ndm - first;
+    if (count < 0) count = p->pb.ndm - first;
     CertState *cert = reinterpret_cast<CertState *>(ws + part_bytes(p));
     const int32_t *list = reinterpret_cast<const int32_t *>(cert + 1);
     p->cert_rechecked = 0;
@@ -2423,8 +2464,8 @@ int resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, double
                              .count();
         }
     } timer{p, t_start};
-    if (p->h_cert->nnonfinite > 0 && p->dtype != PU_U8) {
-        int rc = pu::nonfinite_any_async(data, p->dtype, p->nchan, p->n, ld, &cert->scan, s);
+    if (p->h_cert->nnonfinite > 0 && p->pb.dtype != PU_U8) {
+        int rc = pu::nonfinite_any_async(data, p->pb.dtype, p->pb.nchan, p->pb.n, ld, &cert->scan, s);
         if (rc) return rc;
         PU_TRY_HIP(hipMemcpyAsync(p->h_cert, cert, sizeof(CertState), hipMemcpyDeviceToHost, s));
         PU_TRY_HIP(hipStreamSynchronize(s));
@@ -2443,7 +2484,7 @@ int resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, double
     PU_TRY_HIP(hipMemcpyAsync(idx.data(), list, (size_t)nflag * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     PU_TRY_HIP(hipStreamSynchronize(s));
     std::sort(idx.begin(), idx.end());
-    const int64_t n = p->n, nchan = p->nchan;
+    const int64_t n = p->pb.n, nchan = p->pb.nchan;
     const int64_t per_row = n * 8 + (int64_t)pu_series_stats_workspace_bytes(1, n) + nchan * 8;
     const int64_t B = std::max<int64_t>(1, std::min<int64_t>(nflag, (int64_t(1) << 30) / per_row));
     const size_t plane_b = ((size_t)B * n * sizeof(double) + 255) & ~size_t(255);
@@ -2478,7 +2519,7 @@ int resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, double
         for (auto &v : sh) v = ((v % n) + n) % n;  // row index (t + shift) mod n
         rc = pu::hip_check(hipMemcpyAsync(d_sh, sh.data(), sh.size() * sizeof(int64_t), hipMemcpyHostToDevice, s),
                            "hipMemcpyAsync(recheck shifts)");
-        if (!rc) rc = pu::exact_series(data, p->dtype, nchan, n, ld, d_sh, m, plane, s);
+        if (!rc) rc = pu::exact_series(data, p->pb.dtype, nchan, n, ld, d_sh, m, plane, s);
         if (!rc)
             rc = pu::hip_check(hipMemcpyAsync(d_idx, idx.data() + i0, (size_t)m * sizeof(int32_t),
                                               hipMemcpyHostToDevice, s), "hipMemcpyAsync(recheck index)");
@@ -2490,14 +2531,10 @@ int resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, double
     return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t n, const int64_t *shifts,
-                      int64_t ndm, const pu_plan_opts *opts)
+// The argument checks of pu_plan_create_ex and pu_plan_describe; fills the problem.
+int check_plan_args(int dtype, int acc, int64_t nchan, int64_t n, const int64_t *shifts, int64_t ndm,
+                    const pu_plan_opts *opts, PlanProblem &pb)
 {
-    PU_REQUIRE(out != nullptr, "pu_plan_create: out is NULL");
     PU_REQUIRE(opts != nullptr, "pu_plan_create_ex: opts is NULL");
     const int group = opts->group;
     PU_REQUIRE(opts->shape >= -1 && opts->shape <= 2, "pu_plan_create_ex: shape %d not in {-1, 0, 1, 2}", opts->shape);
@@ -2506,7 +2543,6 @@ int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t 
     PU_REQUIRE(opts->u8_dma >= -1 && opts->u8_dma <= 1 && opts->dt_major >= -1 && opts->dt_major <= 1 &&
                    opts->slot16 >= -1 && opts->slot16 <= 1,
                "pu_plan_create_ex: u8_dma / dt_major / slot16 must be -1, 0 or 1");
-    *out = nullptr;
     const int v = pick_variant(dtype, acc);
     PU_REQUIRE(v >= 0, "pu_plan_create: unsupported dtype %d", dtype);
     PU_REQUIRE(acc >= PU_ACC_NATIVE && acc <= PU_ACC_F64, "pu_plan_create: bad acc %d", acc);
@@ -2519,49 +2555,51 @@ int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t 
                "pu_plan_create: group %d not in {0 (auto), 1, 2, 4, 8}", group);
     if (dtype == PU_U8 && acc != PU_ACC_F64)
         PU_REQUIRE(nchan <= 65793, "pu_plan_create: u8 f32 accumulation exact only for nchan <= 65793");
+    pb.dtype = dtype;
+    pb.acc = acc;
+    pb.variant = v;
+    pb.nchan = nchan;
+    pb.n = n;
+    pb.ndm = ndm;
+    pb.opt_u8_dma = opts->u8_dma < 0 ? 1 : opts->u8_dma;
+    pb.opt_dt_major = opts->dt_major;
+    pb.opt_slot16 = opts->slot16;
+    return PU_OK;
+}
 
-    pu_plan *p = new pu_plan();
-    p->dtype = dtype;
-    p->acc = acc;
-    p->variant = v;
-    p->nchan = nchan;
-    p->n = n;
-    p->ndm = ndm;
-    const int E = 8 / kVariants[v].lds_elem;
-    p->K = E * (kVariants[v].acc_f64 && kVariants[v].lds_elem == 4 ? 2 : 4);  // dedisp_kernel's J
-    p->TT = 64 * p->K;
-    p->ntt = (int)((n + p->TT - 1) / p->TT);
-    p->opt_u8_dma = opts->u8_dma < 0 ? 1 : opts->u8_dma;
-    p->opt_dt_major = opts->dt_major;
-    p->opt_slot16 = opts->slot16;
-
+// The plan for a validated problem: subband mode with the explicit or automatic group size
+// and shape, falling through to smaller groups and then channel mode where a candidate does
+// not fit (PU_EUNSUPPORTED); any other error is returned as is.
+int choose_plan(const PlanProblem &pb, const int64_t *shifts, const pu_plan_opts &opts, PlanTables &out)
+{
+    const int64_t nchan = pb.nchan, n = pb.n;
+    const VariantInfo &vi = kVariants[pb.variant];
     // subband workgroup shape: 0 = wide (1 WG/CU), 1 = pair (2 WGs/CU), 2 = tall (256
     // trials x 256 samples, 1 WG/CU); -1 = the cost model's choice among wide and tall.
     // LDS budget per workgroup (channel / subband mode).  (Diagnostic build: PU_SUB_SHAPE,
     // PU_LDS_BUDGET_KB and PU_GROUP override the options, for A/B sweeps.)
-    const int shape_opt = pu::knob("PU_SUB_SHAPE", opts->shape);
-    const int budget_kb = pu::knob("PU_LDS_BUDGET_KB", opts->lds_budget_kb);
-    int shape = shape_opt < 0 ? SUB_WIDE : std::clamp(shape_opt, 0, 2);
+    const int shape_opt = pu::knob("PU_SUB_SHAPE", opts.shape);
+    const int budget_kb = pu::knob("PU_LDS_BUDGET_KB", opts.lds_budget_kb);
+    const int shape = shape_opt < 0 ? SUB_WIDE : std::clamp(shape_opt, 0, 2);
     // dedisp_f64_kernel: 80 KiB (two workgroups per CU); dedisp_kernel: 64 KiB
-    size_t budget = kVariants[v].fsm ? 80 * 1024 : kLdsBudget, sub_budget = shape == SUB_PAIR ? 80 * 1024 : 160 * 1024;
+    size_t budget = vi.fsm ? 80 * 1024 : kLdsBudget, sub_budget = shape == SUB_PAIR ? 80 * 1024 : 160 * 1024;
     if (budget_kb > 0) budget = sub_budget = (size_t)std::max(8, budget_kb) * 1024;
     // group size: explicit, else the automatic choice (G = 4 where it is not calibrated);
     // float32 accumulation only (the float64 modes keep the reference's sequential
     // channel order)
-    int G = pu::knob("PU_GROUP", group);
+    int G = pu::knob("PU_GROUP", opts.group);
     bool auto_g = false;
     if (G == 0) {
         G = 4;
-        auto_g = !kVariants[v].acc_f64 && nchan > 8;
+        auto_g = !vi.acc_f64 && nchan > 8;
     }
     G = std::min(G, 8);
-    if (kVariants[v].acc_f64) G = 1;
+    if (vi.acc_f64) G = 1;
     while (G > 1 && G >= nchan) G >>= 1;
     // The automatic choice is calibrated on the wide shape with DMA-staged rows (f32, or
     // u8 with n % 4 == 0); elsewhere the default stays G = 4.
-    const bool dma_rows = dtype == PU_F32 || (dtype == PU_U8 && n % 4 == 0);
+    const bool dma_rows = pb.dtype == PU_F32 || (pb.dtype == PU_U8 && n % 4 == 0);
     if (auto_g && (shape != SUB_WIDE || !dma_rows || budget_kb > 0)) auto_g = false;
-    int rc = PU_EUNSUPPORTED;
     if (auto_g) {
         // Default group size: plan G = 8 and G = 4 on the host and keep the cheaper by the
         // measured cost model: LDS bytes + 3.0e6 B-equivalent per (stage,
@@ -2574,8 +2612,8 @@ int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t 
         // and won 10 % at its 5000 trials, which the byte model alone ranks the same way at
         // both): + 200 B-equivalent per window, the middle of the (88, 389) the two
         // measurements allow.
-        auto cost = [](const pu_plan *q) {
-            return (double)q->lds_traffic + 3.0e6 * (double)q->nstages * q->ntt + 200.0 * (double)q->cost_windows16;
+        auto cost = [](const PlanTables &q) {
+            return (double)q.lds_traffic + 3.0e6 * (double)q.nstages * q.ntt + 200.0 * (double)q.cost_windows16;
         };
         // Round 6, per-slot copy sizes for 16-bit slots: fewer stages for both G, G = 8 most
         // (C3 5000 trials tall G = 4 855.9 -> 847.2 ms, G = 8 936.7 -> 885.3; the 625-trial
@@ -2584,24 +2622,8 @@ int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t 
         // B-equivalents, inside the (4.5e6, 1.0e7) that ranks both measurements right; the
         // winner meets the other shapes under the cost above (6e6 for every plan would pick
         // the wide float32 plan at C3: 1066 vs 847 ms).
-        auto cost_tall16 = [](const pu_plan *q) {
-            return (double)q->lds_traffic + 6.0e6 * (double)q->nstages * q->ntt + 200.0 * (double)q->cost_windows16;
-        };
-        auto fresh = [&]() {
-            pu_plan *q = new pu_plan();
-            q->dtype = p->dtype;
-            q->acc = p->acc;
-            q->variant = p->variant;
-            q->nchan = p->nchan;
-            q->n = p->n;
-            q->ndm = p->ndm;
-            q->K = p->K;
-            q->TT = p->TT;
-            q->ntt = p->ntt;
-            q->opt_u8_dma = p->opt_u8_dma;
-            q->opt_slot16 = p->opt_slot16;
-            q->opt_dt_major = p->opt_dt_major;
-            return q;
+        auto cost_tall16 = [](const PlanTables &q) {
+            return (double)q.lds_traffic + 6.0e6 * (double)q.nstages * q.ntt + 200.0 * (double)q.cost_windows16;
         };
         // Round 3: the tall shape (256 trials x 256 samples) competes too, with G = 4 and 8.
         // With the permlane epilogue the same cost model ranks every measured case right:
@@ -2609,44 +2631,50 @@ int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t 
         // 1114; 625 trials 125.6 vs 132.4, tall G4 135.8), C5 tall G4 0.365 (wide 0.374),
         // C4 wide G4 0.581 (100 trials: tall 0.662).  PU_SUB_SHAPE pins the shape.
         const bool try_tall = shape_opt < 0;
-        pu_plan *q = fresh(), *t4 = try_tall ? fresh() : nullptr, *t8 = try_tall ? fresh() : nullptr;
-        const int rc8 = plan_sub(q, shifts, 8, shape, sub_budget);
-        const int rc4 = plan_sub(p, shifts, 4, shape, sub_budget);
-        const int rct4 = t4 ? plan_sub(t4, shifts, 4, SUB_TALL, 160 * 1024) : PU_EUNSUPPORTED;
-        const int rct8 = t8 ? plan_sub(t8, shifts, 8, SUB_TALL, 160 * 1024) : PU_EUNSUPPORTED;
-        for (int r : {rc8, rc4, rct4, rct8}) {
-            if (r != PU_OK && r != PU_EUNSUPPORTED) {
-                for (pu_plan *c : {p, q, t4, t8}) free_plan(c);
-                return r;
-            }
-        }
-        pu_plan *keep = nullptr, *tall = nullptr;
-        if (rct4 == PU_OK && rct8 == PU_OK && t4->slot16 && t8->slot16)
-            tall = cost_tall16(t8) < cost_tall16(t4) ? t8 : t4;
-        for (auto [cand, ok] : {std::pair<pu_plan *, bool>{p, rc4 == PU_OK}, {q, rc8 == PU_OK},
-                                {t4, rct4 == PU_OK && (!tall || tall == t4)}, {t8, rct8 == PU_OK && (!tall || tall == t8)}})
-            if (ok && (!keep || cost(cand) < cost(keep))) keep = cand;
-        for (pu_plan *cand : {p, q, t4, t8})  // losers (p stays when nothing fits: it is reused below)
-            if (cand != keep && (keep || cand != p)) free_plan(cand);
-        if (keep) {
-            rc = upload_sub(keep);
-            if (!rc) rc = finish_plan(keep, shifts);
-            if (rc) {
-                free_plan(keep);
-                return rc;
-            }
-            *out = keep;
+        // candidates in the order a tie keeps the earlier: G = 4, G = 8, tall G = 4, tall G = 8
+        enum { C4, C8, T4, T8, NCAND };
+        PlanTables cand[NCAND];
+        int rcs[NCAND] = {PU_EUNSUPPORTED, PU_EUNSUPPORTED, PU_EUNSUPPORTED, PU_EUNSUPPORTED};
+        rcs[C8] = plan_sub(pb, shifts, 8, shape, sub_budget, cand[C8]);
+        rcs[C4] = plan_sub(pb, shifts, 4, shape, sub_budget, cand[C4]);
+        if (try_tall) rcs[T4] = plan_sub(pb, shifts, 4, SUB_TALL, 160 * 1024, cand[T4]);
+        if (try_tall) rcs[T8] = plan_sub(pb, shifts, 8, SUB_TALL, 160 * 1024, cand[T8]);
+        for (int k : {C8, C4, T4, T8})
+            if (rcs[k] != PU_OK && rcs[k] != PU_EUNSUPPORTED) return rcs[k];
+        // both tall plans with 16-bit slots: only the cheaper by cost_tall16 competes
+        if (rcs[T4] == PU_OK && rcs[T8] == PU_OK && cand[T4].slot16 && cand[T8].slot16)
+            rcs[cost_tall16(cand[T8]) < cost_tall16(cand[T4]) ? T4 : T8] = PU_EUNSUPPORTED;
+        int keep = -1;
+        for (int k = 0; k < NCAND; ++k)
+            if (rcs[k] == PU_OK && (keep < 0 || cost(cand[k]) < cost(cand[keep]))) keep = k;
+        if (keep >= 0) {
+            out = std::move(cand[keep]);
             return PU_OK;
         }
-        reset_tables(p);
         G = 2;  // 8 and 4 do not fit: continue with the smaller groups
     }
-    for (; G > 1 && rc == PU_EUNSUPPORTED; G >>= 1) {
-        rc = plan_sub(p, shifts, G, shape, sub_budget);
-        if (rc == PU_OK) rc = upload_sub(p);
-        if (rc == PU_EUNSUPPORTED) reset_tables(p);
-    }
-    if (rc == PU_EUNSUPPORTED) rc = plan_channels(p, shifts, budget);
+    int rc = PU_EUNSUPPORTED;
+    for (; G > 1 && rc == PU_EUNSUPPORTED; G >>= 1) rc = plan_sub(pb, shifts, G, shape, sub_budget, out);
+    if (rc == PU_EUNSUPPORTED) rc = plan_channels(pb, shifts, budget, out);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t n, const int64_t *shifts,
+                      int64_t ndm, const pu_plan_opts *opts)
+{
+    PU_REQUIRE(out != nullptr, "pu_plan_create: out is NULL");
+    *out = nullptr;
+    PlanProblem pb;
+    int rc = check_plan_args(dtype, acc, nchan, n, shifts, ndm, opts, pb);
+    if (rc) return rc;
+    pu_plan *p = new pu_plan();
+    p->pb = pb;
+    rc = choose_plan(p->pb, shifts, *opts, p->t);
+    if (!rc) rc = p->d.upload(p->t);
     if (!rc) rc = finish_plan(p, shifts);
     if (rc) {
         free_plan(p);
@@ -2677,7 +2705,7 @@ void pu_plan_destroy(pu_plan *p) { free_plan(p); }
 int pu_plan_enable_timing(pu_plan *p, int nslots)
 {
     PU_REQUIRE(p != nullptr && nslots >= 0 && nslots <= 65536, "pu_plan_enable_timing: bad arguments");
-    std::lock_guard<std::mutex> guard(p->lock.m);
+    std::lock_guard<std::mutex> guard(p->lock);
     destroy_events(p);
     for (auto *v : {&p->ev_start, &p->ev_stop}) {
         v->assign((size_t)nslots, nullptr);
@@ -2690,7 +2718,7 @@ int pu_plan_enable_timing(pu_plan *p, int nslots)
 int pu_plan_stamps(pu_plan *p, int64_t *out, int n)
 {
     PU_REQUIRE(p != nullptr && out != nullptr, "pu_plan_stamps: bad arguments");
-    std::lock_guard<std::mutex> guard(p->lock.m);
+    std::lock_guard<std::mutex> guard(p->lock);
 #ifdef PU_STAMPS
     if (!p->d_stamps) {
         PU_TRY_HIP(hipMalloc((void **)&p->d_stamps, 8 * sizeof(uint64_t)));
@@ -2713,7 +2741,7 @@ int pu_plan_stamps(pu_plan *p, int64_t *out, int n)
 int pu_plan_kernel_times(pu_plan *p, float *ms, int n)
 {
     PU_REQUIRE(p != nullptr && ms != nullptr, "pu_plan_kernel_times: bad arguments");
-    std::lock_guard<std::mutex> guard(p->lock.m);
+    std::lock_guard<std::mutex> guard(p->lock);
     const int64_t have = std::min<int64_t>(p->launches, (int64_t)p->ev_start.size());
     const int m = (int)std::min<int64_t>(n, have);
     for (int i = 0; i < m; ++i) {
@@ -2727,38 +2755,61 @@ size_t pu_plan_workspace_bytes(const pu_plan *p)
 {
     if (!p) return 0;
     // per-(trial, time tile) partial records | CertState | flagged-trial list
-    return part_bytes(p) + sizeof(CertState) + (size_t)p->ndm * sizeof(int32_t);
+    return part_bytes(p) + sizeof(CertState) + (size_t)p->pb.ndm * sizeof(int32_t);
 }
 
 // which kernel a plan's searches launch: 0 dedisp_kernel (channel order), 1 dedisp_f64_kernel,
 // 2 dedisp_sub_kernel (float32 slots), 3 dedisp_sub_kernel with 16-bit integer slots
-static int64_t plan_kernel(const pu_plan *p)
+static int64_t plan_kernel(const PlanProblem &pb, const PlanTables &t)
 {
-    if (p->group > 1) return p->slot16 ? 3 : 2;
-    return kVariants[p->variant].fsm ? 1 : 0;
+    if (t.group > 1) return t.slot16 ? 3 : 2;
+    return kVariants[pb.variant].fsm ? 1 : 0;
 }
 
-int pu_plan_info(const pu_plan *p, int64_t *info, int n)
+// pu_plan_info's fields; cert: {rechecked, nan, why[3], us} of the last call
+static int fill_info(const PlanProblem &pb, const PlanTables &t, const int64_t (&cert)[6], int64_t *info, int n)
 {
-    if (!p || !info) return 0;
-    std::lock_guard<std::mutex> guard(p->lock.m);
-    const int64_t v[] = {p->ndm, p->ndt, p->ntt, p->group > 1 ? with_shape(p->shape, [](auto c) { return decltype(c)::T; }) : kTPT, p->TT, p->ncc,
-                         p->row_stride, (int64_t)p->lds_bytes, kVariants[p->variant].acc_f64, p->max_spread,
-                         p->group, p->nslots_total, p->nstages, (int64_t)p->slot_bytes, p->raw_stride,
-                         p->exec_adds, p->lds_traffic, p->cert_rechecked, p->cert_nan, p->cert_why[0],
-                         p->cert_why[1], p->cert_why[2], p->cert_us, plan_kernel(p), (int64_t)part_elem(p),
+    const int64_t v[] = {pb.ndm, t.ndt, t.ntt, t.group > 1 ? with_shape(t.shape, [](auto c) { return decltype(c)::T; }) : kTPT, t.TT, t.ncc,
+                         t.row_stride, (int64_t)t.lds_bytes, kVariants[pb.variant].acc_f64, t.max_spread,
+                         t.group, t.nslots_total, t.nstages, (int64_t)t.slot_bytes, t.raw_stride,
+                         t.exec_adds, t.lds_traffic, cert[0], cert[1], cert[2],
+                         cert[3], cert[4], cert[5], plan_kernel(pb, t), (int64_t)part_elem(pb),
                          kPartStride};
     const int m = std::min<int>(n, (int)(sizeof v / sizeof v[0]));
     for (int k = 0; k < m; ++k) info[k] = v[k];
     return m;
 }
 
+int pu_plan_info(const pu_plan *p, int64_t *info, int n)
+{
+    if (!p || !info) return 0;
+    std::lock_guard<std::mutex> guard(p->lock);
+    const int64_t cert[6] = {p->cert_rechecked, p->cert_nan, p->cert_why[0], p->cert_why[1], p->cert_why[2], p->cert_us};
+    return fill_info(p->pb, p->t, cert, info, n);
+}
+
+int pu_plan_describe(int dtype, int acc, int64_t nchan, int64_t n, const int64_t *shifts, int64_t ndm,
+                     const pu_plan_opts *opts, int64_t *info, int ninfo, uint64_t *tables_digest)
+{
+    PU_REQUIRE(ninfo >= 0 && (info != nullptr || ninfo == 0), "pu_plan_describe: info is NULL");
+    PlanProblem pb;
+    PlanTables t;
+    int rc = check_plan_args(dtype, acc, nchan, n, shifts, ndm, opts, pb);
+    if (!rc) rc = choose_plan(pb, shifts, *opts, t);
+    if (rc) return rc;
+    pad_slots(t);
+    const int64_t no_cert[6] = {0, 0, 0, 0, 0, 0};
+    fill_info(pb, t, no_cert, info, ninfo);
+    if (tables_digest) *tables_digest = digest_tables(t);
+    return PU_OK;
+}
+
 static int check_data(const pu_plan *p, const void *data, int64_t ld)
 {
     PU_REQUIRE(p != nullptr, "plan is NULL");
     PU_REQUIRE(data != nullptr, "data is NULL");
-    PU_REQUIRE(ld >= p->n, "ld %lld < nsamples %lld", (long long)ld, (long long)p->n);
-    PU_REQUIRE(!p->dma8 || (reinterpret_cast<uintptr_t>(data) % 4 == 0 && ld % 4 == 0),
+    PU_REQUIRE(ld >= p->pb.n, "ld %lld < nsamples %lld", (long long)ld, (long long)p->pb.n);
+    PU_REQUIRE(!p->t.dma8 || (reinterpret_cast<uintptr_t>(data) % 4 == 0 && ld % 4 == 0),
                "8-bit subband plan: rows must start on 4-byte boundaries (data %% 4 == 0, ld %% 4 == 0)");
     return PU_OK;
 }
@@ -2768,15 +2819,15 @@ static DedispArgs make_args(const pu_plan *p, const void *data, int64_t ld)
     DedispArgs a{};
     a.data = data;
     a.ld = ld;
-    a.nchan = (int32_t)p->nchan;
-    a.n = (int32_t)p->n;
-    a.ndt = p->ndt;
-    a.ntt = p->ntt;
+    a.nchan = (int32_t)p->pb.nchan;
+    a.n = (int32_t)p->pb.n;
+    a.ndt = p->t.ndt;
+    a.ntt = p->t.ntt;
     a.tt0 = 0;
-    a.ntt_run = p->ntt;
-    a.ncc = p->ncc;
-    a.row_stride = p->row_stride;
-    a.small_n = p->small_n;
+    a.ntt_run = p->t.ntt;
+    a.ncc = p->t.ncc;
+    a.row_stride = p->t.row_stride;
+    a.small_n = p->t.small_n;
     return a;
 }
 
@@ -2785,10 +2836,10 @@ int pu_plan_search_tiles(pu_plan *p, const void *data, int64_t ld, int64_t tt_be
 {
     int rc = check_data(p, data, ld);
     if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock.m);
-    PU_REQUIRE(0 <= tt_begin && tt_begin <= tt_end && tt_end <= p->ntt,
+    std::lock_guard<std::mutex> guard(p->lock);
+    PU_REQUIRE(0 <= tt_begin && tt_begin <= tt_end && tt_end <= p->t.ntt,
                "pu_plan_search_tiles: tile range [%lld, %lld) outside [0, %d)", (long long)tt_begin,
-               (long long)tt_end, p->ntt);
+               (long long)tt_end, p->t.ntt);
     PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p), "pu_plan_search_tiles: workspace too small");
     if (tt_begin == tt_end) return PU_OK;
     DedispArgs a = make_args(p, data, ld);
@@ -2803,7 +2854,7 @@ int pu_plan_finalize(pu_plan *p, const void *data, int64_t ld, double *max_out, 
 {
     int rc = check_data(p, data, ld);
     if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock.m);
+    std::lock_guard<std::mutex> guard(p->lock);
     PU_REQUIRE(max_out && std_out && snr_out && rebin_out, "pu_plan_finalize: NULL output");
     PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
                "pu_plan_finalize: workspace too small or not 8-byte aligned");
@@ -2820,10 +2871,10 @@ int pu_plan_finalize_range(pu_plan *p, const void *data, int64_t ld, int64_t tri
 {
     int rc = check_data(p, data, ld);
     if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock.m);
-    PU_REQUIRE(0 <= trial_begin && trial_begin <= trial_end && trial_end <= p->ndm,
+    std::lock_guard<std::mutex> guard(p->lock);
+    PU_REQUIRE(0 <= trial_begin && trial_begin <= trial_end && trial_end <= p->pb.ndm,
                "pu_plan_finalize_range: trial range [%lld, %lld) outside [0, %lld)", (long long)trial_begin,
-               (long long)trial_end, (long long)p->ndm);
+               (long long)trial_end, (long long)p->pb.ndm);
     PU_REQUIRE(max_out && std_out && snr_out && rebin_out, "pu_plan_finalize_range: NULL output");
     PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
                "pu_plan_finalize_range: workspace too small or not 8-byte aligned");
@@ -2841,10 +2892,10 @@ int pu_plan_finalize_range_flagged(pu_plan *p, int64_t trial_begin, int64_t tria
                                    size_t ws_bytes, int32_t *flagged, int64_t cap, int64_t *counts, void *stream)
 {
     PU_REQUIRE(p != nullptr, "plan is NULL");
-    std::lock_guard<std::mutex> guard(p->lock.m);
-    PU_REQUIRE(0 <= trial_begin && trial_begin <= trial_end && trial_end <= p->ndm,
+    std::lock_guard<std::mutex> guard(p->lock);
+    PU_REQUIRE(0 <= trial_begin && trial_begin <= trial_end && trial_end <= p->pb.ndm,
                "pu_plan_finalize_range_flagged: trial range [%lld, %lld) outside [0, %lld)", (long long)trial_begin,
-               (long long)trial_end, (long long)p->ndm);
+               (long long)trial_end, (long long)p->pb.ndm);
     PU_REQUIRE(max_out && std_out && snr_out && rebin_out && counts && (flagged || cap == 0),
                "pu_plan_finalize_range_flagged: NULL output");
     PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
@@ -2879,17 +2930,17 @@ int pu_plan_exact_series(pu_plan *p, const void *data, int64_t ld, const int32_t
 {
     int rc = check_data(p, data, ld);
     if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock.m);
-    PU_REQUIRE(0 <= t_begin && t_begin <= t_end && t_end <= p->n, "pu_plan_exact_series: samples [%lld, %lld) outside [0, %lld)",
-               (long long)t_begin, (long long)t_end, (long long)p->n);
+    std::lock_guard<std::mutex> guard(p->lock);
+    PU_REQUIRE(0 <= t_begin && t_begin <= t_end && t_end <= p->pb.n, "pu_plan_exact_series: samples [%lld, %lld) outside [0, %lld)",
+               (long long)t_begin, (long long)t_end, (long long)p->pb.n);
     PU_REQUIRE(m >= 0, "pu_plan_exact_series: m < 0");
     if (m == 0 || t_end == t_begin) return PU_OK;
     PU_REQUIRE(trials && out, "pu_plan_exact_series: NULL trials / out");
-    const int64_t n = p->n, nchan = p->nchan;
+    const int64_t n = p->pb.n, nchan = p->pb.nchan;
     std::vector<int64_t> sh((size_t)(m * nchan));
     for (int64_t k = 0; k < m; ++k) {
-        PU_REQUIRE(0 <= trials[k] && trials[k] < p->ndm, "pu_plan_exact_series: trial %d outside [0, %lld)",
-                   trials[k], (long long)p->ndm);
+        PU_REQUIRE(0 <= trials[k] && trials[k] < p->pb.ndm, "pu_plan_exact_series: trial %d outside [0, %lld)",
+                   trials[k], (long long)p->pb.ndm);
         std::copy_n(p->shifts.data() + (size_t)trials[k] * nchan, nchan, sh.data() + k * nchan);
     }
     for (auto &v : sh) v = ((v % n) + n) % n;
@@ -2899,7 +2950,7 @@ int pu_plan_exact_series(pu_plan *p, const void *data, int64_t ld, const int32_t
     rc = pu::hip_check(hipMemcpyAsync(d_sh, sh.data(), sh.size() * sizeof(int64_t), hipMemcpyHostToDevice, s),
                        "hipMemcpyAsync(exact series shifts)");
     if (!rc)
-        rc = pu::exact_series(data, p->dtype, nchan, n, ld, reinterpret_cast<const int64_t *>(d_sh), m, out, s, t_begin,
+        rc = pu::exact_series(data, p->pb.dtype, nchan, n, ld, reinterpret_cast<const int64_t *>(d_sh), m, out, s, t_begin,
                               t_end - t_begin);
     (void)hipFreeAsync(d_sh, s);
     const int rs = pu::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(exact series)");
@@ -2923,7 +2974,7 @@ int pu_plan_search(pu_plan *p, const void *data, int64_t ld, double *max_out, do
 {
     int rc = check_data(p, data, ld);
     if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock.m);
+    std::lock_guard<std::mutex> guard(p->lock);
     PU_REQUIRE(max_out && std_out && snr_out && rebin_out, "pu_plan_search: NULL output");
     PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
                "pu_plan_search: workspace too small or not 8-byte aligned");
@@ -2946,9 +2997,9 @@ int pu_plan_dedisperse(pu_plan *p, const void *data, int64_t ld, void *plane, in
 {
     int rc = check_data(p, data, ld);
     if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock.m);
+    std::lock_guard<std::mutex> guard(p->lock);
     PU_REQUIRE(plane != nullptr, "pu_plan_dedisperse: plane is NULL");
-    PU_REQUIRE(ld_plane >= p->n, "pu_plan_dedisperse: ld_plane < nsamples");
+    PU_REQUIRE(ld_plane >= p->pb.n, "pu_plan_dedisperse: ld_plane < nsamples");
     DedispArgs a = make_args(p, data, ld);
     a.plane = plane;
     a.ld_plane = ld_plane;
@@ -2958,11 +3009,11 @@ int pu_plan_dedisperse(pu_plan *p, const void *data, int64_t ld, void *plane, in
 int pu_plan_dm_tiles(const pu_plan *p, int32_t *first, int32_t *count, int n)
 {
     if (!p) return 0;
-    std::lock_guard<std::mutex> guard(p->lock.m);
-    const int ndt = (int)p->tile_first.size();
+    std::lock_guard<std::mutex> guard(p->lock);
+    const int ndt = (int)p->t.tile_first.size();
     for (int t = 0; t < std::min(n, ndt); ++t) {
-        if (first) first[t] = p->tile_first[t];
-        if (count) count[t] = p->tile_count[t];
+        if (first) first[t] = p->t.tile_first[t];
+        if (count) count[t] = p->t.tile_count[t];
     }
     return ndt;
 }
@@ -2972,19 +3023,19 @@ int pu_plan_dedisperse_dm_tile(pu_plan *p, const void *data, int64_t ld, int64_t
 {
     int rc = check_data(p, data, ld);
     if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock.m);
+    std::lock_guard<std::mutex> guard(p->lock);
     PU_REQUIRE(plane != nullptr, "pu_plan_dedisperse_dm_tile: plane is NULL");
-    PU_REQUIRE(ld_plane >= p->n, "pu_plan_dedisperse_dm_tile: ld_plane < nsamples");
-    PU_REQUIRE(0 <= dt && dt < (int64_t)p->tile_first.size(), "pu_plan_dedisperse_dm_tile: DM tile %lld outside [0, %d)",
-               (long long)dt, (int)p->tile_first.size());
+    PU_REQUIRE(ld_plane >= p->pb.n, "pu_plan_dedisperse_dm_tile: ld_plane < nsamples");
+    PU_REQUIRE(0 <= dt && dt < (int64_t)p->t.tile_first.size(), "pu_plan_dedisperse_dm_tile: DM tile %lld outside [0, %d)",
+               (long long)dt, (int)p->t.tile_first.size());
     DedispArgs a = make_args(p, data, ld);
     a.dt0 = (int32_t)dt;
     a.ndt = 1;
     // the kernels write trial row (first + i) at plane + (first + i) ld_plane: shift the base
     // so that the tile's rows land at rows 0 .. count - 1 of the caller's plane
-    const size_t elem = kVariants[p->variant].acc_f64 ? sizeof(double) : sizeof(float);
+    const size_t elem = kVariants[p->pb.variant].acc_f64 ? sizeof(double) : sizeof(float);
     a.plane = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(plane) -
-                                       (uintptr_t)((size_t)p->tile_first[(size_t)dt] * (size_t)ld_plane * elem));
+                                       (uintptr_t)((size_t)p->t.tile_first[(size_t)dt] * (size_t)ld_plane * elem));
     a.ld_plane = ld_plane;
     return dispatch(p, a, true, pu::as_stream(stream));
 }

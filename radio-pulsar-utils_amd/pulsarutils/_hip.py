@@ -30,6 +30,7 @@ SIGNATURES = {
     "pu_plan_create": (_i32, [ctypes.POINTER(_vp), _i32, _i32, _i64, _i64, _vp, _i64]),
     "pu_plan_create_grouped": (_i32, [ctypes.POINTER(_vp), _i32, _i32, _i64, _i64, _vp, _i64, _i32]),
     "pu_plan_create_ex": (_i32, [ctypes.POINTER(_vp), _i32, _i32, _i64, _i64, _vp, _i64, _vp]),
+    "pu_plan_describe": (_i32, [_i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
     "pu_plan_destroy": (None, [_vp]),
     "pu_plan_workspace_bytes": (_sz, [_vp]),
     "pu_plan_search": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -234,6 +235,32 @@ def to_device(a, allowed=(PU_U8, PU_F32, PU_F64), device=None):
     return x.contiguous()
 
 
+def _plan_inputs(nchan, shifts, group, shape, lds_budget_kb, u8_dma, dt_major, slot16):
+    """The shift table as the library reads it and ``pu_plan_opts`` from ``Plan``'s keywords."""
+    sh = np.ascontiguousarray(shifts, dtype=np.int64)
+    if sh.ndim != 2 or sh.shape[1] != int(nchan):
+        raise ValueError(f"shift table must be (ndm, {nchan}) int64, got shape {sh.shape}")
+    opts = PlanOpts(group=int(group), shape=-1 if shape is None else int(SHAPES.get(shape, shape)),
+                    lds_budget_kb=int(lds_budget_kb), u8_dma=-1 if u8_dma is None else int(bool(u8_dma)),
+                    dt_major=-1 if dt_major is None else int(bool(dt_major)),
+                    slot16=-1 if slot16 is None else int(bool(slot16)))
+    return sh, opts
+
+
+def describe_plan(dtype_code_, acc, nchan, nsamples, shifts, group=0, shape=None, lds_budget_kb=0,
+                  u8_dma=None, dt_major=None, slot16=None):
+    """pu_plan_describe: what ``Plan`` with the same arguments would build, planned on the
+    host alone (no GPU needed) - ``(info, tables_digest)``: ``Plan.info``'s fields with the
+    certification fields 0, and the 64-bit digest of the tables the plan would upload."""
+    sh, opts = _plan_inputs(nchan, shifts, group, shape, lds_budget_kb, u8_dma, dt_major, slot16)
+    info = np.zeros(len(INFO_FIELDS), np.int64)
+    digest = ctypes.c_uint64()
+    check(lib().pu_plan_describe(dtype_code_, acc, nchan, nsamples, sh.ctypes.data_as(ctypes.c_void_p), sh.shape[0],
+                                 ctypes.byref(opts), info.ctypes.data_as(ctypes.c_void_p), len(INFO_FIELDS),
+                                 ctypes.byref(digest)), "pu_plan_describe")
+    return dict(zip(INFO_FIELDS, info.tolist())), digest.value
+
+
 class Plan:
     """Owning wrapper of a ``pu_plan`` (dedispersion tiling + device metadata)."""
 
@@ -249,14 +276,8 @@ class Plan:
         slots).  These are the planner's only inputs (pu_plan_create_ex): the
         library reads no environment."""
         require_gpu()
-        sh = np.ascontiguousarray(shifts, dtype=np.int64)
-        if sh.ndim != 2 or sh.shape[1] != int(nchan):
-            raise ValueError(f"shift table must be (ndm, {nchan}) int64, got shape {sh.shape}")
+        sh, opts = _plan_inputs(nchan, shifts, group, shape, lds_budget_kb, u8_dma, dt_major, slot16)
         ndm = sh.shape[0]
-        opts = PlanOpts(group=int(group), shape=-1 if shape is None else int(SHAPES.get(shape, shape)),
-                        lds_budget_kb=int(lds_budget_kb), u8_dma=-1 if u8_dma is None else int(bool(u8_dma)),
-                        dt_major=-1 if dt_major is None else int(bool(dt_major)),
-                        slot16=-1 if slot16 is None else int(bool(slot16)))
         h = ctypes.c_void_p()
         check(lib().pu_plan_create_ex(ctypes.byref(h), dtype_code_, acc, nchan, nsamples,
                                       sh.ctypes.data_as(ctypes.c_void_p), ndm, ctypes.byref(opts)),

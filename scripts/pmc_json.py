@@ -4,7 +4,7 @@ profiles/pmc_<tag>.json (bench.py reads it).
 Usage: python scripts/pmc_json.py <pmc dir> <tag> <bench json> [kernel substring]
 
 <pmc dir> holds the two rocprofv3 passes of one bench command: p1 (--pmc FETCH_SIZE)
-and p2 (--pmc WRITE_SIZE), as scripts/r03_refresh.sh collects them.  The average over
+and p2 (--pmc WRITE_SIZE), as scripts/refresh.sh collects them.  The average over
 the kernel's dispatches is corrected as /opt/skills/guides/MI355X_MICROARCH.md §HBM
 prescribes for gfx950 (FETCH_SIZE x 2 for 16-B/lane streaming reads - the LDS-DMA
 dwordx4 row loads here; WRITE_SIZE as is; KB = 1024 B).  The summary records the

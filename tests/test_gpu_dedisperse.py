@@ -728,3 +728,28 @@ def test_c3_plan_choice_shard_and_full(gpu):
         sh = _hip.shift_table(c.nchan, dms[:ntr], c.start_freq, c.bandwidth, c.tsamp)
         info = _hip.Plan(_hip.PU_U8, _hip.PU_ACC_NATIVE, c.nchan, c.nsamples, sh).info
         assert (info["group"], info["kernel"], info["trials_per_tile"]) == (group, kernel, 256), (ntr, info)
+
+
+def _describe_case(name):
+    """(dtype code, acc, nchan, nsamples, shifts, options) of a plan the CPU suite pins
+    (tests/test_plan_tables.py)."""
+    if name == "u8_small":
+        sh = _hip.shift_table(64, np.linspace(0, 50, 40), 400., 100., 1e-3)
+        return _hip.PU_U8, _hip.PU_ACC_NATIVE, 64, 4096, sh, dict(group=4, shape="tall")
+    c = CONFIGS[name]
+    dms = D.dedispersion_plan(c.nchan, c.dmmin, c.dmmax, c.start_freq, c.bandwidth, c.tsamp)
+    sh = _hip.shift_table(c.nchan, dms, c.start_freq, c.bandwidth, c.tsamp)
+    return {"f32": _hip.PU_F32, "f64": _hip.PU_F64}[c.dtype], _hip.PU_ACC_NATIVE, c.nchan, c.nsamples, sh, {}
+
+
+@pytest.mark.parametrize("name", ["u8_small", "C5", "C1"])
+def test_plan_info_equals_describe_plan(gpu, name):
+    """The plan built on the device is the plan the host-only planner describes: every info
+    field outside the certification outcome (which only a search fills) is equal."""
+    dtype, acc, nchan, n, sh, opts = _describe_case(name)
+    info = _hip.Plan(dtype, acc, nchan, n, sh, **opts).info
+    described, _ = _hip.describe_plan(dtype, acc, nchan, n, sh, **opts)
+    assert described.keys() == info.keys()
+    for k in info:
+        if not k.startswith("cert_"):
+            assert info[k] == described[k], (k, info[k], described[k])
