@@ -416,6 +416,18 @@ int pu_roll_and_sum(const void *x, int dtype, int64_t n, int64_t roll, double *s
 int pu_transpose(const void *src, int elem_bytes, int64_t rows, int64_t cols, int64_t ld_src,
                  void *dst, int64_t ld_dst, void *stream);
 
+/* Unpack + transpose a block of packed SIGPROC samples: src is time-major, one spectrum
+ * per row of ld_src BYTES, channel c of a spectrum in bits [c*nbits, (c+1)*nbits) counted
+ * from the least-significant bit of byte 0 (sigproc / sigpyproc order: the first channel
+ * sits in the low bits).  dst[c * ld_dst + t] =
+ *     (src[t * ld_src + (c * nbits) / 8] >> ((c * nbits) % 8)) & ((1 << nbits) - 1)
+ * as uint8, channel-major (nchans rows of ld_dst >= nsamps).  nbits 1, 2 or 4;
+ * nchans * nbits must be a multiple of 8; ld_src >= nchans * nbits / 8.  src needs no
+ * alignment (ld_src may be odd).  Replaces the unpack + transpose of sigpyproc's
+ * readBlock (clean.py:327, stats.py:45). */
+int pu_unpack_transpose(const void *src, int nbits, int64_t nsamps, int64_t nchans,
+                        int64_t ld_src, uint8_t *dst, int64_t ld_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

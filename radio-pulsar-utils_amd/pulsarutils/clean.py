@@ -535,6 +535,8 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
     ``renormalize_data``; band flipped when ``foff < 0``; resampled by
     ``N = rint(new_sample_time / tsamp)`` when >= 2; ``dedispersion_search``.  All array
     work stays in HBM (read_block_device -> renormalize_device -> HIP rebin -> search).
+    1-, 2- and 4-bit files are uploaded packed and unpacked to uint8 on the device
+    (``FilReader.device_block``); from there on they are 8-bit files.
 
     ``search_dtype``: the renormalised chunk is float64 (clean.py:73); ``"f64"``
     (default, the reference's behaviour, clean.py:346) searches it with float64
@@ -555,7 +557,7 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
     import pickle
     import time
     from .dedispersion import _rebin_time_device, delta_delay, search_device
-    from .sigproc import FilReader, transpose_device
+    from .sigproc import FilReader
     from .stats import get_bad_chans
     if search_dtype not in ("f32", "f64"):
         raise ValueError(f"search_dtype must be 'f32' or 'f64', got {search_dtype!r}")
@@ -638,7 +640,7 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
             tc = np.ascontiguousarray(fil._block_tc(istart, chunk_size))
             src = t.from_numpy(tc).to(dev)
         mark("h2d")
-        block = transpose_device(src)
+        block = fil.device_block(src)  # (1/2/4-bit files: uploaded packed, unpacked to uint8 here)
         del src
         mark("transpose")
         if _hip.dtype_code(block.dtype) is None:
