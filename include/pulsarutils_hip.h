@@ -428,6 +428,31 @@ int pu_transpose(const void *src, int elem_bytes, int64_t rows, int64_t cols, in
 int pu_unpack_transpose(const void *src, int nbits, int64_t nsamps, int64_t nchans,
                         int64_t ld_src, uint8_t *dst, int64_t ld_dst, void *stream);
 
+/* Quantise + pack + transpose a cleaned block back to SIGPROC sample rows: the inverse of
+ * pu_unpack_transpose, and the array step of cleanup_data (clean.py:354-356, a stub in the
+ * reference: the requantisation below is this project's definition).  src is channel-major,
+ * nchans rows of ld_src ELEMENTS of type dtype (PU_U8 / PU_F32 / PU_F64); dst is time-major,
+ * nsamps rows of ld_dst BYTES.  scale, offset: device [nchans] float64, or both NULL for
+ * identity (one NULL and one not: PU_EINVAL).
+ *     v = (double)src[c * ld_src + t] * scale[c] + offset[c]      (v = x in identity mode)
+ * with the multiply and the add rounded separately (no FMA).
+ *  nbits 1, 2, 4, 8:  a NaN v is replaced by offset[c] (0 in identity mode: a cleaned sample
+ *     of an all-zero channel lands on the mean level), then
+ *     q = min(max(rint(v), 0), 2^nbits - 1), rint rounding half to even as np.rint; +-inf
+ *     clamp like any other value.  q goes to bits [c*nbits, (c+1)*nbits) of row t counted
+ *     from the least-significant bit of byte 0 (at 8 bits the byte is q).  nchans * nbits
+ *     must be a multiple of 8; ld_dst >= nchans * nbits / 8; a row's bytes beyond that are
+ *     not written.
+ *  nbits 32:  row t holds nchans float32 (float)v, round to nearest, no clamp, NaN stays
+ *     NaN; ld_dst >= 4 * nchans, dst and ld_dst multiples of 4.
+ * src needs the alignment of its element type only and dst none (ld_src and ld_dst may be
+ * odd): the access widths follow the pointers and leading dimensions.  PU_EUNSUPPORTED for
+ * other nbits / dtypes, PU_EINVAL for bad sizes, PU_OK without a launch for an empty block;
+ * all checked before any HIP call. */
+int pu_quantize_pack_transpose(const void *src, int dtype, int64_t nchans, int64_t nsamps, int64_t ld_src,
+                               const double *scale, const double *offset, int nbits,
+                               void *dst, int64_t ld_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,7 @@ SIGNATURES = {
     "pu_roll_and_sum": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp]),
     "pu_transpose": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp]),
     "pu_unpack_transpose": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "pu_quantize_pack_transpose": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _vp]),
     "pu_stream_create_cu_masked": (_i32, [_i32, ctypes.POINTER(_vp)]),
     "pu_stream_destroy": (_i32, [_vp]),
 }

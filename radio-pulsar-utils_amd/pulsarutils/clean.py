@@ -692,6 +692,164 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
     return candidates
 
 
-__all__ = ["search_by_chunks", "PulseInfo", "get_noisier_channels", "renormalize_data", "measure_channel_variability",
+# cleanup_data's default (out_mean, out_sigma) per output width
+_OUT_LEVELS = {1: (0.5, 0.5), 2: (1.5, 1.0), 4: (7.5, 2.5), 8: (96.0, 16.0)}
+
+
+def cleanup_data(fname, outname, nbits=8, chunksize=2**17, surelybad=(), baseline_window=101, cut_outliers=False,
+                 zero_dm=False, out_mean=None, out_sigma=None, profile=None):
+    """clean.py:354-356 ("Clean the data", a two-line stub in the reference): stream a SIGPROC
+    file through the cleaning pass and write the cleaned data to ``outname`` as a SIGPROC file
+    of ``nbits`` (1, 2, 4, 8 or 32) bits.  The reference's two positional arguments come
+    first; everything else is this project's addition.
+
+    Channel mask: ``get_bad_chans(fname)`` plus ``surelybad``; ``mean_spec, std_spec =
+    get_spectral_stats(fname)`` (one pass over the file serves both when the mask is not
+    cached yet).
+
+    Output levels: a renormalised good channel ``(x - mu) / mu`` has the standard deviation
+    ``sig_c = std_spec[c] / mean_spec[c]``; it is written as ``rint(v * scale[c] + offset[c])``
+    clipped to ``[0, 2**nbits - 1]`` with ``offset[c] = out_mean`` and ``scale[c] = out_sigma /
+    sig_c`` (float64, on the host) - 0 where the channel is masked or ``sig_c`` is not finite
+    and positive, so a masked or dead channel becomes the constant ``rint(out_mean)`` (a NaN
+    sample, of an all-zero channel, lands there too).  ``out_mean, out_sigma`` default by
+    ``nbits`` to ``{1: (0.5, 0.5), 2: (1.5, 1.0), 4: (7.5, 2.5), 8: (96.0, 16.0)}``: this
+    project's choice, with no reference counterpart.  ``nbits=32`` applies no scale or offset
+    and writes the float32 of the renormalised plane.
+
+    Chunks are ``chunksize`` samples long and do not overlap; a tail shorter than ``chunksize
+    // 2`` is merged into the chunk before it (a file shorter than ``chunksize`` is one chunk).
+    Every input sample is written exactly once, in file channel order (no band flip: ``foff``
+    and ``fch1`` carry over); the output header is the input's with ``nbits`` replaced and
+    ``nifs = 1``.  Per chunk: upload -> ``FilReader.device_block`` -> ``renormalize_device``
+    -> quantise, transpose and pack on the device (``sigproc.quantize_pack_device``), so only
+    ``nbits / 8`` bytes per sample come back.  The device-to-host copy (pinned double buffer,
+    a copy stream) and the file write (one writer thread) of chunk k run while chunk k + 1 is
+    uploaded and cleaned.  ``profile``: a list that receives one dict of synchronised per-step
+    timings (ms: h2d, transpose, clean, quantize, d2h, write) per chunk; no overlap then.
+
+    Returns a dict: nsamples, nchunks, nbits, mask, scale, offset (scale and offset None for
+    ``nbits=32``)."""
+    import time
+    from .sigproc import FilReader, FilWriter, quantize_pack_device
+    from .stats import get_bad_chans, get_spectral_stats
+    nbits = int(nbits)
+    if nbits not in (1, 2, 4, 8, 32):
+        raise ValueError(f"cleanup_data: nbits must be 1, 2, 4, 8 or 32, got {nbits}")
+    chunksize = int(chunksize)
+    if chunksize < 1:
+        raise ValueError("cleanup_data: chunksize must be positive")
+    t = _hip.require_gpu()
+    mean_spec, std_spec = get_spectral_stats(fname)
+    mask = np.array(get_bad_chans(fname, stats=(mean_spec, std_spec)), dtype=bool)
+    for bad_chan in surelybad:
+        mask[bad_chan] = True
+    fil = FilReader(fname)
+    nsamples, nchan = fil.header["nsamples"], fil.header["nchans"]
+    scale = offset = None
+    if nbits != 32:
+        dflt = _OUT_LEVELS[nbits]
+        out_mean = float(dflt[0] if out_mean is None else out_mean)
+        out_sigma = float(dflt[1] if out_sigma is None else out_sigma)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sig = std_spec / mean_spec
+        ok = ~mask & np.isfinite(sig) & (sig > 0)
+        scale = np.zeros(nchan, dtype=np.float64)
+        scale[ok] = out_sigma / sig[ok]
+        offset = np.full(nchan, out_mean, dtype=np.float64)
+    chunks = [(i, min(chunksize, nsamples - i)) for i in range(0, nsamples, chunksize)]
+    if len(chunks) > 1 and chunks[-1][1] < chunksize // 2:
+        last = chunks.pop()
+        chunks[-1] = (chunks[-1][0], chunks[-1][1] + last[1])
+    dev = t.device("cuda", t.cuda.current_device())
+    dscale = t.from_numpy(scale).to(dev) if scale is not None else None
+    doffset = t.from_numpy(offset).to(dev) if offset is not None else None
+    # The packed rows of chunk k are copied to one of two pinned buffers on a copy stream and
+    # written by a writer thread once the copy's event has fired, while the current stream
+    # uploads and cleans chunk k + 1.  With ``profile`` every step is synchronised instead.
+    overlap = profile is None and len(chunks) > 1
+    pool = copy_stream = None
+    pinned, busy = [None, None], [None, None]
+
+    def clean_chunk(istart, size, mark):
+        tc = np.ascontiguousarray(fil._block_tc(istart, size))
+        src = t.from_numpy(tc).to(dev)
+        mark("h2d")
+        block = fil.device_block(src)  # (1/2/4-bit files: uploaded packed, unpacked to uint8 here)
+        del src
+        mark("transpose")
+        if _hip.dtype_code(block.dtype) is None:
+            block = block.to(t.float64)
+        array, _ = renormalize_device(block, badchans_mask=mask, baseline_window=baseline_window,
+                                      cut_outliers=cut_outliers, zero_dm=zero_dm)
+        del block
+        mark("clean")
+        packed = quantize_pack_device(array, nbits, dscale, doffset)
+        mark("quantize")
+        return packed
+
+    with FilWriter(outname, fil.header, nbits=nbits) as writer:
+        if overlap:
+            from concurrent.futures import ThreadPoolExecutor
+            pool = ThreadPoolExecutor(max_workers=1)
+            copy_stream = t.cuda.Stream(device=dev)
+            nmax = max(size for _, size in chunks) * writer.row_bytes
+            pinned = [t.empty(nmax, dtype=t.uint8).pin_memory() for _ in range(2)]
+
+            def write_when_copied(done, rows, packed):
+                # (``packed`` rides along: the tensor stays alive until its copy is done)
+                with t.cuda.device(dev):
+                    done.synchronize()
+                writer.write_rows(rows.numpy())
+
+        try:
+            for k, (istart, size) in enumerate(chunks):
+                marks = []
+
+                def mark(name):
+                    if profile is not None:
+                        t.cuda.synchronize()
+                        marks.append((name, time.perf_counter()))
+
+                mark("start")
+                packed = clean_chunk(istart, size, mark)
+                if overlap:
+                    slot = k % 2
+                    if busy[slot] is not None:
+                        busy[slot].result()  # the write of chunk k - 2 has left this buffer
+                    cur = t.cuda.current_stream(dev)
+                    ready = t.cuda.Event()
+                    ready.record(cur)
+                    raw = packed.view(t.uint8)
+                    rows = pinned[slot][:raw.numel()].view(raw.shape)
+                    with t.cuda.stream(copy_stream):
+                        copy_stream.wait_event(ready)
+                        rows.copy_(raw, non_blocking=True)
+                        done = t.cuda.Event()
+                        done.record(copy_stream)
+                    packed.record_stream(copy_stream)
+                    busy[slot] = pool.submit(write_when_copied, done, rows, packed)
+                else:
+                    rows = packed.cpu().numpy()
+                    mark("d2h")
+                    writer.write_rows(rows)
+                    mark("write")
+                    if profile is not None:
+                        rec = {"istart": istart, "nsamples": size}
+                        rec.update({name: (tt - marks[i][1]) * 1e3 for i, (name, tt) in enumerate(marks[1:])})
+                        profile.append(rec)
+                del packed
+            for fut in busy:
+                if fut is not None:
+                    fut.result()
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True)
+        written = writer.nsamples
+    return {"nsamples": written, "nchunks": len(chunks), "nbits": nbits, "mask": mask, "scale": scale,
+            "offset": offset}
+
+
+__all__ = ["search_by_chunks", "cleanup_data", "PulseInfo", "get_noisier_channels", "renormalize_data", "measure_channel_variability",
            "dedispersion_search", "digitize", "dm_broadening", "renormalize_device",
            "channel_means_device", "channel_variances_device", "make_table"]

@@ -104,6 +104,39 @@ def _unpack(packed, nbits):
                                                                                         packed.shape[1] * (8 // nbits))
 
 
+# the order header keys are written in (strings, then integers, then doubles); a key the
+# header does not hold is skipped
+_HEADER_ORDER = ("source_name", "rawdatafile",
+                 "machine_id", "telescope_id", "data_type", "barycentric", "pulsarcentric", "nchans", "nbits", "nifs",
+                 "nbeams", "ibeam",
+                 "fch1", "foff", "tstart", "tsamp", "az_start", "za_start", "src_raj", "src_dej", "refdm", "period")
+# what read_header derives from the file rather than reads from it
+_DERIVED_KEYS = ("nsamples", "bandwidth", "ftop", "fbottom", "fcenter", "hdrlen")
+
+
+def _header_bytes(hdr):
+    """The SIGPROC header of the keys in ``hdr``, written in ``_HEADER_ORDER``."""
+    def s(x):
+        b = x.encode()
+        return struct.pack("<i", len(b)) + b
+
+    unknown = sorted(set(hdr) - set(_HEADER_ORDER))
+    if unknown:
+        raise ValueError(f"unknown SIGPROC header key(s) {unknown}")
+    out = [s("HEADER_START")]
+    for k in _HEADER_ORDER:
+        if k not in hdr:
+            continue
+        if k in _STR_KEYS:
+            out += [s(k), s(str(hdr[k]))]
+        elif k in _INT_KEYS:
+            out += [s(k), struct.pack("<i", int(hdr[k]))]
+        else:
+            out += [s(k), struct.pack("<d", float(hdr[k]))]
+    out.append(s("HEADER_END"))
+    return b"".join(out)
+
+
 def write_filterbank(fname, data_tc, fch1, foff, tsamp, tstart=60000.0, source_name="synthetic", nbits=None):
     """Write a time-major (nsamps, nchans) array as a SIGPROC filterbank file.
 
@@ -114,21 +147,100 @@ def write_filterbank(fname, data_tc, fch1, foff, tsamp, tstart=60000.0, source_n
     if nbits in _PACKED:
         data_tc = _pack(data_tc, nbits)
     nbits = nbits or {np.dtype(np.uint8): 8, np.dtype(np.uint16): 16, np.dtype(np.float32): 32}[data_tc.dtype]
-
-    def s(x):
-        b = x.encode()
-        return struct.pack("<i", len(b)) + b
-
-    out = [s("HEADER_START"), s("source_name"), s(source_name)]
-    for k, v in (("machine_id", 0), ("telescope_id", 0), ("data_type", 1), ("nchans", nchans),
-                 ("nbits", nbits), ("nifs", 1)):
-        out += [s(k), struct.pack("<i", v)]
-    for k, v in (("fch1", fch1), ("foff", foff), ("tstart", tstart), ("tsamp", tsamp)):
-        out += [s(k), struct.pack("<d", v)]
-    out.append(s("HEADER_END"))
+    hdr = {"source_name": source_name, "machine_id": 0, "telescope_id": 0, "data_type": 1, "nchans": nchans,
+           "nbits": nbits, "nifs": 1, "fch1": fch1, "foff": foff, "tstart": tstart, "tsamp": tsamp}
     with open(fname, "wb") as f:
-        f.write(b"".join(out))
+        f.write(_header_bytes(hdr))
         f.write(data_tc.tobytes())
+
+
+class FilWriter:
+    """Streaming SIGPROC writer (a context manager): the header goes out at open, sample rows
+    are appended block by block, so a file never has to exist whole in memory.
+
+    ``header``: a dict as in :attr:`FilReader.header`.  The keys read_header derives
+    (``nsamples, bandwidth, ftop, fbottom, fcenter, hdrlen``) are dropped, ``nifs`` is
+    written as 1 (blocks hold one IF) and ``nbits`` (when given) replaces the header's value;
+    every other key must be one of the module's ``_INT_KEYS`` / ``_DBL_KEYS`` / ``_STR_KEYS``
+    (``ValueError`` otherwise) and is written through unchanged, in the fixed order
+    ``_HEADER_ORDER``: source_name, rawdatafile; machine_id, telescope_id, data_type,
+    barycentric, pulsarcentric, nchans, nbits, nifs, nbeams, ibeam; fch1, foff, tstart, tsamp,
+    az_start, za_start, src_raj, src_dej, refdm, period.  ``nchans, fch1, foff, tsamp`` are
+    required (FilReader cannot open a file without them).
+
+    ``write_block`` takes host time-major samples, ``write_block_device`` a channel-major
+    device block (quantised, transposed and packed on the GPU, pu_quantize_pack_transpose:
+    only ``nbits / 8`` bytes per sample cross PCIe), ``write_rows`` rows that are packed
+    already.  ``nsamples`` counts the spectra written so far."""
+
+    def __init__(self, fname, header, nbits=None):
+        hdr = {k: v for k, v in dict(header).items() if k not in _DERIVED_KEYS}
+        missing = [k for k in ("nchans", "fch1", "foff", "tsamp") if k not in hdr]
+        if missing:
+            raise ValueError(f"FilWriter: header lacks {missing}")
+        hdr["nifs"] = 1
+        hdr["nbits"] = int(nbits if nbits is not None else hdr.get("nbits", 8))
+        self.nbits, self.nchans = hdr["nbits"], int(hdr["nchans"])
+        if self.nbits not in _DTYPES and self.nbits not in _PACKED:
+            raise ValueError(f"FilWriter: nbits={self.nbits} not supported (1, 2, 4, 8, 16, 32)")
+        if self.nchans < 1 or self.nchans * self.nbits % 8:
+            raise ValueError(f"FilWriter: nchans={self.nchans} x nbits={self.nbits} is not a whole number of bytes "
+                             "per spectrum")
+        head = _header_bytes(hdr)  # (an unknown key raises before the file is created)
+        self.filename = fname
+        self.header = hdr
+        self.row_bytes = self.nchans * self.nbits // 8
+        self.nsamples = 0
+        self._f = open(fname, "wb")
+        self._f.write(head)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        """Flush and close the file; further calls do nothing."""
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def write_rows(self, rows):
+        """Append packed host rows: a 2-D array whose rows are ``row_bytes`` bytes each."""
+        if self._f is None:
+            raise ValueError("FilWriter: the file is closed")
+        rows = np.ascontiguousarray(rows)
+        if rows.ndim != 2 or rows.shape[1] * rows.itemsize != self.row_bytes:
+            raise ValueError(f"FilWriter: rows of {self.row_bytes} bytes expected, got shape {rows.shape} of "
+                             f"{rows.dtype}")
+        self._f.write(rows.data)
+        self.nsamples += rows.shape[0]
+
+    def write_block(self, data_tc):
+        """Append a host time-major (nsamps, nchans) block: an integer array below ``2**nbits``
+        for 1-, 2- and 4-bit output (packed by ``_pack``), otherwise an array of the file's
+        dtype (uint8, uint16 or float32), written as it is."""
+        data_tc = np.asarray(data_tc)
+        if data_tc.ndim != 2 or data_tc.shape[1] != self.nchans:
+            raise ValueError(f"FilWriter: a (nsamps, {self.nchans}) block expected, got shape {data_tc.shape}")
+        if self.nbits in _PACKED:
+            rows = _pack(np.ascontiguousarray(data_tc), self.nbits)
+        elif data_tc.dtype != np.dtype(_DTYPES[self.nbits]):
+            raise ValueError(f"FilWriter: {self.nbits}-bit output takes {np.dtype(_DTYPES[self.nbits])} blocks, got "
+                             f"{data_tc.dtype}")
+        else:
+            rows = data_tc
+        self.write_rows(rows)
+
+    def write_block_device(self, x, scale=None, offset=None):
+        """Append a channel-major (nchans, nsamps) device block through
+        :func:`quantize_pack_device` (``nbits`` 1, 2, 4, 8 or 32); synchronises on the copy."""
+        if self.nbits not in (1, 2, 4, 8, 32):
+            raise ValueError(f"FilWriter: write_block_device writes 1, 2, 4, 8 or 32 bits, not {self.nbits}")
+        if x.dim() != 2 or x.shape[0] != self.nchans:
+            raise ValueError(f"FilWriter: a ({self.nchans}, nsamps) block expected, got shape {tuple(x.shape)}")
+        self.write_rows(quantize_pack_device(x, self.nbits, scale, offset).cpu().numpy())
 
 
 class FilReader:
@@ -215,4 +327,53 @@ def unpack_transpose_device(src, nbits, nchans):
     ld_src = src.stride(0) if nsamps > 1 else max(src.stride(0), src.shape[1])
     _hip.check(_hip.lib().pu_unpack_transpose(_hip.ptr(src), nbits, nsamps, nchans, ld_src, _hip.ptr(out),
                                               nsamps, _hip.stream_ptr()), "pu_unpack_transpose")
+    return out
+
+
+def quantize_pack_device(x, nbits, scale=None, offset=None):
+    """Channel-major (nchans, nsamps) device block -> SIGPROC sample rows on the device: the
+    inverse of :func:`unpack_transpose_device` (pu_quantize_pack_transpose).
+
+    ``v = x[c, t] * scale[c] + offset[c]`` in float64 (``v = x`` when both are None); for
+    ``nbits`` 1, 2, 4, 8 a NaN becomes ``offset[c]`` (0 without an offset), ``q = clip(rint(v),
+    0, 2**nbits - 1)`` is packed in the bit order of the module docstring and the result is a
+    contiguous ``(nsamps, nchans * nbits / 8)`` uint8 tensor; ``nbits == 32`` returns
+    ``(nsamps, nchans)`` float32 of ``v`` (no clamp, NaN kept).  ``x``: uint8, float32 or
+    float64 with unit column stride and any row stride; ``scale``, ``offset``: numpy or device
+    float64 ``[nchans]``."""
+    from . import _hip
+    t = _hip.require_gpu()
+    nbits = int(nbits)
+    code = _hip.dtype_code(x.dtype) if isinstance(x, t.Tensor) else None
+    if (code not in (_hip.PU_U8, _hip.PU_F32, _hip.PU_F64) or x.dim() != 2 or not x.is_cuda
+            or (x.shape[1] > 1 and x.stride(1) != 1)):
+        raise ValueError("quantize_pack_device: a 2-D uint8 / float32 / float64 CUDA tensor with unit column stride")
+    nchans, nsamps = x.shape
+
+    def vec(a, name):
+        if a is None:
+            return None
+        if not isinstance(a, t.Tensor):
+            a = t.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+        a = a.to(x.device)
+        if a.dtype != t.float64 or tuple(a.shape) != (nchans,):
+            raise ValueError(f"quantize_pack_device: {name} must be float64 of shape ({nchans},), got {a.dtype} "
+                             f"{tuple(a.shape)}")
+        return a.contiguous()
+
+    scale, offset = vec(scale, "scale"), vec(offset, "offset")
+    if nbits == 32:
+        out = t.empty((nsamps, nchans), dtype=t.float32, device=x.device)
+    else:
+        # (a width the library does not write, or a partial byte per spectrum, is its error to raise)
+        out = t.empty((nsamps, nchans * nbits // 8), dtype=t.uint8, device=x.device)
+    valid = nbits == 32 or (nbits in _PACKED + (8,) and nchans * nbits % 8 == 0)
+    if valid and (scale is None) == (offset is None) and x.numel() == 0:
+        return out  # (an empty tensor has no pointer to pass)
+    # a single row's stride is arbitrary in torch: any value >= the row's length will do
+    ld_src = x.stride(0) if nchans > 1 else max(x.stride(0), nsamps)
+    _hip.check(_hip.lib().pu_quantize_pack_transpose(_hip.ptr(x), code, nchans, nsamps, ld_src, _hip.ptr(scale),
+                                                     _hip.ptr(offset), nbits, _hip.ptr(out),
+                                                     out.shape[1] * out.element_size(), _hip.stream_ptr()),
+               "pu_quantize_pack_transpose")
     return out

@@ -85,17 +85,18 @@ def get_spectral_stats(fname, chunksize=10000, show=False):
     return mean_spec, std_spec
 
 
-def get_bad_chans(fname, show=False, cache=None):
+def get_bad_chans(fname, show=False, cache=None, stats=None):
     """stats.py:63-90: channels above medfilt(11) + 4 ref_mad in the mean or std spectrum.
 
     Cached as one text row in ``fname + '.badchans'`` (``np.savetxt(fmt='%g')``), reused
-    when present, as in the reference.
+    when present, as in the reference.  ``stats``: the file's ``get_spectral_stats`` result
+    when the caller has it already (cleanup_data), so the file is not read a second time.
     """
     if cache is None:
         cache = fname + ".badchans"
     if os.path.exists(cache):
         return np.loadtxt(cache).astype(bool)
-    mean_spec, mean_std = get_spectral_stats(fname, show=show)
+    mean_spec, mean_std = stats if stats is not None else get_spectral_stats(fname, show=show)
     badchans = np.zeros(mean_spec.size, dtype=bool)
     chans = np.arange(mean_spec.size)
     for spec in (mean_spec, mean_std):
