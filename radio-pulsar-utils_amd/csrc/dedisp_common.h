@@ -663,16 +663,32 @@ __device__ __forceinline__ void write_outputs(const Ta (&acc)[D][K], const Dedis
     if constexpr (STATS) {
         // Per trial: lane-local stats of the 1/2/4/8-sample rebinned sums in the
         // accumulation type (few terms), then float64 wave reductions.
+        const bool full = t0 + J * 64 * E <= n;  // uniform
+        auto bcast = [](Ta v, int from) {
+            if constexpr (sizeof(Ta) == 4) {
+                return __builtin_bit_cast(Ta, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), from));
+            } else {
+                const uint64_t b = __builtin_bit_cast(uint64_t, v);
+                return __builtin_bit_cast(Ta, (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, from) |
+                                                  ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), from) << 32));
+            }
+        };
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             if (slot0 + d >= cnt) continue;
-            Ta kt;  // lane 0's first sample: the shift that keeps the sums well conditioned
-            if constexpr (sizeof(Ta) == 4) {
-                kt = __builtin_bit_cast(Ta, __builtin_amdgcn_readlane(__builtin_bit_cast(int, acc[d][0]), 0));
-            } else {
-                const uint64_t b = __builtin_bit_cast(uint64_t, acc[d][0]);
-                kt = __builtin_bit_cast(Ta, (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 0) |
-                                                ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), 0) << 32));
+            // The shift that keeps the sums well conditioned.  A full tile: lane 0's first
+            // sample (one tile of many: the finalize kernel recentres it).  A partial tile -
+            // the last of a series, or a short series' only one - holds few windows, whose
+            // squares about the first sample are w^2 (x_0 - mean)^2 each and would round, in
+            // the accumulation type of the record, by more than the windows' variance times the
+            // tolerance of a float32 search: the mean of the tile's samples instead.
+            Ta kt = bcast(acc[d][0], 0);
+            if (!full) {
+                Ta s = Ta(0);
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                    if (sample(k) < n) s += acc[d][k];
+                kt = bcast(static_cast<Ta>(wave_sum_to63_acc<Ta>(s) / (double)(n - t0)), 63);
             }
             Ta mx[4], s1[4], s2[4];
 #pragma unroll
@@ -716,7 +732,6 @@ __device__ __forceinline__ void write_outputs(const Ta (&acc)[D][K], const Dedis
                 }
             }
             Ta *p = reinterpret_cast<Ta *>(a.partials) + ((size_t)(first + slot0 + d) * a.ntt + tt) * kPartStride;
-            const bool full = t0 + J * 64 * E <= n;  // uniform
             double x1_0 = 0.0;
 #pragma unroll
             for (int w = 0; w < 4; ++w) {

@@ -46,11 +46,18 @@ def quick_chan_rebin(counts, current_rebin):
     """dedispersion.py:15-35: sum groups of ``current_rebin`` channels, channel order.
 
     Output dtype follows ``np.sum``: float32->float32, float64->float64,
-    unsigned ints->uint64, signed ints/bool->int64 (integer sums are exact).
+    unsigned ints->uint64, signed ints/bool->int64 (integer sums are exact), for numpy
+    arrays and torch tensors alike.
     """
     t = _hip.require_gpu()
     out_np_dtype = None
-    if not isinstance(counts, t.Tensor):
+    if isinstance(counts, t.Tensor):
+        if not (counts.dtype.is_floating_point or counts.dtype.is_complex):
+            unsigned = counts.dtype in (t.uint8, t.uint16, t.uint32, t.uint64)
+            out_np_dtype = np.uint64 if unsigned else np.int64
+            if counts.dtype != t.uint8:
+                counts = counts.to(t.int64)
+    else:
         counts = np.asarray(counts)
         k = counts.dtype.kind
         if k in "iub":
@@ -251,11 +258,24 @@ def dedispersion_search(data, dmmin, dmmax, start_freq, bandwidth, sample_time, 
 def apply_dm_shifts_to_data(data, shifts):
     """dedispersion.py:254-258: roll channel i by ``-rint(shifts[i])`` (input dtype kept).
 
-    The roll is a pure element move, done on the raw bits of 1/4/8-byte elements.
+    The roll is a pure element move, done on the raw bits of 1/4/8-byte elements (numpy
+    arrays and torch tensors; 2-byte integers are widened and narrowed back exactly).
     """
     t = _hip.require_gpu()
     view_back = None
-    if not isinstance(data, t.Tensor):
+    if isinstance(data, t.Tensor):
+        # the same on a tensor: raw 1/4/8-byte elements; 2-byte integers widened to int64 and
+        # narrowed back on the device (exact)
+        tensor_dtype = data.dtype
+        size_code = {1: t.uint8, 4: t.float32, 8: t.float64}
+        if data.element_size() in size_code:
+            data = data.contiguous().view(size_code[data.element_size()])
+        elif tensor_dtype in (t.int16, t.uint16):
+            data = data.contiguous().view(t.int16).to(t.int64)
+        else:
+            tensor_dtype = None  # (float16 / bfloat16: through float64, returned as float64)
+    else:
+        tensor_dtype = None
         data = np.ascontiguousarray(data)
         size_code = {1: np.uint8, 4: np.float32, 8: np.float64}
         if data.dtype.itemsize in size_code:
@@ -273,6 +293,10 @@ def apply_dm_shifts_to_data(data, shifts):
     out = t.empty_like(x)
     _hip.check(_hip.lib().pu_roll_rows(_hip.ptr(x), _hip.dtype_code(x.dtype), nchan, n, x.stride(0), _hip.ptr(dsh),
                                        _hip.ptr(out), _hip.stream_ptr()), "apply_dm_shifts_to_data")
+    if tensor_dtype is not None:
+        if tensor_dtype in (t.int16, t.uint16):
+            out = out.to(t.int16)
+        out = out.view(tensor_dtype)
     res = _numpy_out(out)
     if view_back is not None:
         res = res.view(view_back) if res.dtype.itemsize == np.dtype(view_back).itemsize else res.astype(view_back)

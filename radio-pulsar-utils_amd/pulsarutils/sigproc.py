@@ -296,12 +296,17 @@ class FilReader:
 
 
 def transpose_device(src):
-    """(rows, cols) -> (cols, rows) contiguous, HIP tiled transpose (1/2/4/8-byte elements)."""
+    """(rows, cols) -> (cols, rows) contiguous, HIP tiled transpose (1/2/4/8-byte elements).
+    ``src`` may have any row stride; its columns must be adjacent (unit column stride)."""
     from . import _hip
     t = _hip.require_gpu()
+    if src.dim() != 2 or not src.is_cuda or (src.shape[1] > 1 and src.stride(1) != 1):
+        raise ValueError("transpose_device: a 2-D CUDA tensor with unit column stride")
     rows, cols = src.shape
     out = t.empty((cols, rows), dtype=src.dtype, device=src.device)
-    _hip.check(_hip.lib().pu_transpose(_hip.ptr(src), src.element_size(), rows, cols, src.stride(0), _hip.ptr(out),
+    # a single row's stride is arbitrary in torch: any value >= the row's length will do
+    ld_src = src.stride(0) if rows > 1 else max(src.stride(0), cols)
+    _hip.check(_hip.lib().pu_transpose(_hip.ptr(src), src.element_size(), rows, cols, ld_src, _hip.ptr(out),
                                        rows, _hip.stream_ptr()), "pu_transpose")
     return out
 

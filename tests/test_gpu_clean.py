@@ -713,3 +713,91 @@ def test_stream_ptr_is_torch_current_stream(gpu):
         assert (_hip.stream_ptr().value or 0) == s.cuda_stream
     assert (_hip.stream_ptr(s).value or 0) == s.cuda_stream
     assert (_hip.stream_ptr().value or 0) == torch.cuda.current_stream().cuda_stream
+
+
+# ------------------------------------------------------------------ small n
+# The chunk lengths search_by_chunks reaches at its minimum step (64-128 samples and a shorter
+# tail) and the n < 64 branch of renormalize_device (scipy on the host + pu_zero_columns).
+# sigma = n // 100 * 2 + 1 is 1 below n = 100, 3 from 100 and 5 at 200; the gaussian's radius
+# (4, 12, 20) exceeds n at the small sizes, so the reflection wraps more than once.
+SMALL_N = [1, 2, 15, 16, 17, 63, 64, 65, 80, 99, 100, 101, 127, 128, 199, 200]
+
+
+def small_case(n, nchan, dt):
+    """Positive noise around 60 with a broadband spike five bins before the end (n >= 8)."""
+    rng = np.random.default_rng(1000 * nchan + n)
+    x = rng.standard_normal((nchan, n)) * 6 + 60
+    if n >= 8:
+        x[:, n - 5] += 80
+    if dt == "u8":
+        return np.clip(np.rint(x), 0, 255).astype(np.uint8)
+    return x.astype({"f32": np.float32, "f64": np.float64}[dt])
+
+
+@pytest.fixture
+def outlier_calls(gpu, monkeypatch):
+    """Counts the calls of the two outlier-cut entry points (the device path and the n < 64
+    host path's column zeroing), which compute the same thing by design."""
+    from pulsarutils import _hip
+    lib = _hip.lib()
+    calls = {"pu_cut_outliers": 0, "pu_zero_columns": 0}
+
+    def spy(name):
+        fn = getattr(lib, name)
+
+        def wrapped(*a):
+            calls[name] += 1
+            return fn(*a)
+        monkeypatch.setattr(lib, name, wrapped)
+
+    for name in calls:
+        spy(name)
+    return calls
+
+
+@pytest.mark.parametrize("mode", ["plain", "cut", "zero_dm", "cut_zero_dm"])
+@pytest.mark.parametrize("dt", ["u8", "f32", "f64"])
+def test_renormalize_small_n(gpu, outlier_calls, dt, mode):
+    """renormalize_data bit-equal to the oracle for n from 1 to 200 and 1-3 channels."""
+    kw = dict(cut_outliers="cut" in mode, zero_dm="zero_dm" in mode)
+    for nchan in (1, 2, 3):
+        for n in SMALL_N:
+            x = small_case(n, nchan, dt)
+            before = dict(outlier_calls)
+            got = C.renormalize_data(x, **kw)
+            want, bins = co.renormalize(x, return_badbins=True, **kw)
+            assert np.isfinite(want).all(), (nchan, n)
+            assert got.dtype == np.float64 and got.shape == want.shape
+            assert np.array_equal(got, want), (nchan, n, np.argwhere(got != want)[:5].tolist())
+            if not kw["cut_outliers"]:
+                assert outlier_calls == before
+                continue
+            device = outlier_calls["pu_cut_outliers"] - before["pu_cut_outliers"]
+            zeroed = outlier_calls["pu_zero_columns"] - before["pu_zero_columns"]
+            # 64 samples and more: decided on the device; fewer: on the host, and the cut bins
+            # (if any) zeroed by pu_zero_columns
+            assert (device, zeroed) == ((1, 0) if n >= 64 else (0, int(bins.any()))), (nchan, n)
+            if n == 63:   # the spike case: the oracle cuts some bins, not all
+                assert 0 < bins.sum() < n and not want[:, bins].any()
+                assert kw["zero_dm"] or want[:, ~bins].any()   # (zero-DM of one channel is all zeros)
+
+
+def test_renormalize_small_n_masked_channel(gpu, outlier_calls):
+    """One of three channels masked, at every small n, with the cut and the bad_bins mask."""
+    import torch
+    from pulsarutils import _hip
+    bad = np.array([False, True, False])
+    for dt in ("u8", "f32", "f64"):
+        for n in SMALL_N:
+            x = small_case(n, 3, dt)
+            for zero_dm in (False, True):
+                out, bins = C.renormalize_device(_hip.to_device(x), badchans_mask=bad, cut_outliers=True,
+                                                 zero_dm=zero_dm)
+                want, wbins = co.renormalize(x, badchans_mask=bad, cut_outliers=True, zero_dm=zero_dm,
+                                             return_badbins=True)
+                got = out.cpu().numpy()
+                assert np.isfinite(want).all() and not want[1].any()
+                assert np.array_equal(got, want), (dt, n, zero_dm, np.argwhere(got != want)[:5].tolist())
+                assert bins.dtype == torch.bool
+                np.testing.assert_array_equal(bins.cpu().numpy(), wbins)
+    assert outlier_calls["pu_zero_columns"] > 0 and outlier_calls["pu_cut_outliers"] > 0
