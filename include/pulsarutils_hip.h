@@ -198,6 +198,36 @@ int pu_series_stats(const double *series, int64_t rows, int64_t n, int64_t ld,
                     const int32_t *index, double *max_out, double *std_out, double *snr_out,
                     int32_t *rebin_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Single-pulse events of float64 dedispersed series (this project's definition; the
+ * quantities are those of dedispersion.py:186-201, in the same numpy order as
+ * pu_series_stats).  For each row d (rows x n, leading dimension ld) and threshold
+ * (finite, > 0):
+ *   s = d - np.mean(d)
+ *   for window w in 1, 2, 4, 8 with nb = n // w >= 1:
+ *       reb = quick_resample(s, w), sd = np.std(reb)
+ *       sd not finite or not > 0: no events of this window
+ *       bin i is above when reb[i] / sd > threshold (one IEEE division; NaN compares false)
+ *       an event is a maximal run [start, start + nbins) of consecutive above bins (the
+ *       series is linear: no run wraps from nb - 1 to 0); peak = the first bin of the run
+ *       where reb is largest; snr = reb[peak] / sd.
+ * So a row has an event iff the reference's snr of it exceeds threshold, and its largest
+ * event snr then equals that snr bit for bit.  Events are delivered sorted by (input row r,
+ * window, start); pu_event.row is index[r] (device int32; NULL = r).  *count (host)
+ * receives the total number of events; the first min(*count, cap) are written to events
+ * (device; may be NULL when cap == 0: the call then only counts).  workspace: 256-byte
+ * aligned device memory; rows are processed in batches of as many as
+ * pu_series_events_workspace_bytes(batch, n) <= workspace_bytes allows (at least one) and
+ * the result does not depend on the batch size.  Synchronises stream once. */
+typedef struct pu_event {
+    int32_t row, window;
+    int64_t start, nbins, peak;
+    double snr;
+} pu_event;
+size_t pu_series_events_workspace_bytes(int64_t rows, int64_t n);
+int pu_series_events(const double *series, int64_t rows, int64_t n, int64_t ld, const int32_t *index,
+                     double threshold, pu_event *events, int64_t cap, int64_t *count, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 /* Replaces dedisperse (dedispersion.py:93-98) for every trial of the plan: writes
  * the dedispersed plane plane[trial * ld_plane + t] in the accumulation type
  * (float32 or float64), the show=True plane of dedispersion_search (:214-227). */

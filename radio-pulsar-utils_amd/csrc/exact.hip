@@ -324,49 +324,82 @@ __global__ void nan_rule_kernel(int64_t ndm, double *max_out, double *std_out, d
 
 unsigned grid_for(int64_t n, int64_t cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, (n + 255) / 256)); }
 
-// Workspace carve-up for R rows of n samples.
+// Workspace carve-up for R rows of n samples.  R[k] is the buffer of the 2^k-sample rebinned
+// series (R[0] = S): one shared buffer for the statistics, which need each rebinning only
+// until its moments are taken, one each for the events, which read them all afterwards.
 struct StatsWs {
-    double *S, *R, *mean, *mw, *var;
+    double *S, *R[4], *mean, *mw, *var;
     uint64_t *keys;
     void *rs;
     size_t rs_bytes;
+    int64_t *blk, *total;  // events only: per-workgroup run-start counts / offsets, running total
 };
+
+size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+// Workgroups of the event stage per row: one per kEvBlock bins of each window.
+constexpr int kEvPerLane = 8;
+constexpr int kEvWave = 64 * kEvPerLane;  // consecutive bins a wave owns
+constexpr int kEvBlock = 4 * kEvWave;     // bins per workgroup
+
+int64_t event_blocks(int64_t n)
+{
+    int64_t t = 0;
+    for (int k = 0; k < 4; ++k) t += ((n >> k) + kEvBlock - 1) / kEvBlock;
+    return t;
+}
 
 size_t stats_bytes(int64_t rows, int64_t n)
 {
-    const size_t a = 256;
-    auto up = [&](size_t b) { return (b + a - 1) / a * a; };
-    return up(rows * n * 8) + up(rows * (n / 2) * 8) + up(pu_row_sums_workspace_bytes(rows, n)) +
-           up(rows * 8) + 2 * up(4 * rows * 8) + up(4 * rows * 8);
+    return up256(rows * n * 8) + up256(rows * (n / 2) * 8) + up256(pu_row_sums_workspace_bytes(rows, n)) +
+           up256(rows * 8) + 2 * up256(4 * rows * 8) + up256(4 * rows * 8);
 }
 
-StatsWs carve(void *ws, int64_t rows, int64_t n)
+size_t events_bytes(int64_t rows, int64_t n)
 {
-    const size_t a = 256;
-    auto up = [&](size_t b) { return (b + a - 1) / a * a; };
+    return stats_bytes(rows, n) + up256(rows * (n / 4) * 8) + up256(rows * (n / 8) * 8) +
+           up256(rows * event_blocks(n) * 8) + 256;
+}
+
+StatsWs carve(void *ws, int64_t rows, int64_t n, bool events = false)
+{
     char *p = reinterpret_cast<char *>(ws);
     StatsWs w;
+    w.blk = w.total = nullptr;
+    if (events) {  // the running total first: at the same place for every batch size
+        w.total = reinterpret_cast<int64_t *>(p);
+        p += 256;
+    }
     w.S = reinterpret_cast<double *>(p);
-    p += up(rows * n * 8);
-    w.R = reinterpret_cast<double *>(p);
-    p += up(rows * (n / 2) * 8);
+    p += up256(rows * n * 8);
+    w.R[0] = w.S;
+    w.R[1] = w.R[2] = w.R[3] = reinterpret_cast<double *>(p);
+    p += up256(rows * (n / 2) * 8);
     w.rs = p;
     w.rs_bytes = pu_row_sums_workspace_bytes(rows, n);
-    p += up(w.rs_bytes);
+    p += up256(w.rs_bytes);
     w.mean = reinterpret_cast<double *>(p);
-    p += up(rows * 8);
+    p += up256(rows * 8);
     w.mw = reinterpret_cast<double *>(p);
-    p += up(4 * rows * 8);
+    p += up256(4 * rows * 8);
     w.var = reinterpret_cast<double *>(p);
-    p += up(4 * rows * 8);
+    p += up256(4 * rows * 8);
     w.keys = reinterpret_cast<uint64_t *>(p);
+    p += up256(4 * rows * 8);
+    if (events) {
+        w.R[2] = reinterpret_cast<double *>(p);
+        p += up256(rows * (n / 4) * 8);
+        w.R[3] = reinterpret_cast<double *>(p);
+        p += up256(rows * (n / 8) * 8);
+        w.blk = reinterpret_cast<int64_t *>(p);
+    }
     return w;
 }
 
-int stats_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const int32_t *idx, double *max_out,
-                double *std_out, double *snr_out, int32_t *win_out, void *ws, hipStream_t s)
+// The part pu_series_stats and pu_series_events share: mean, S = row - mean, the rebinned
+// series R[k] (row stride n >> k), the variance of each (numpy's order) and the max keys.
+int stats_moments(const double *plane, int64_t rows, int64_t n, int64_t ld, const StatsWs &w, hipStream_t s)
 {
-    StatsWs w = carve(ws, rows, n);
     const dim3 blk(256);
     int rc = pu_row_sums(plane, PU_F64, rows, n, ld, 0, nullptr, nullptr, (double)n, w.mean, w.rs, w.rs_bytes, s);
     if (rc) return rc;
@@ -378,13 +411,12 @@ int stats_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const 
         const int win = 1 << k;
         const int64_t nb = n / win;
         if (nb == 0) break;
-        const double *src = w.S;
         if (k > 0) {
             hipLaunchKernelGGL(exact_rebin_kernel, dim3(grid_for(nb, 64), (unsigned)rows), blk, 0, s, w.S, n, win, nb,
-                               w.R, w.keys + k * rows);
+                               w.R[k], w.keys + k * rows);
             if ((rc = pu::launch_check("exact_rebin_kernel"))) return rc;
-            src = w.R;
         }
+        const double *src = w.R[k];
         // np.std(reb): mean, then the sum of squared deviations, both in numpy's order
         rc = pu_row_sums(src, PU_F64, rows, nb, nb, 0, nullptr, nullptr, (double)nb, w.mw + k * rows, w.rs,
                          w.rs_bytes, s);
@@ -393,9 +425,189 @@ int stats_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const 
                              w.rs, w.rs_bytes, s);
         if (rc) return rc;
     }
+    return PU_OK;
+}
+
+int stats_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const int32_t *idx, double *max_out,
+                double *std_out, double *snr_out, int32_t *win_out, void *ws, hipStream_t s)
+{
+    StatsWs w = carve(ws, rows, n);
+    int rc = stats_moments(plane, rows, n, ld, w, s);
+    if (rc) return rc;
     hipLaunchKernelGGL(exact_final_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, rows, n, w.keys, w.var,
                        idx, max_out, std_out, snr_out, win_out);
     return pu::launch_check("exact_final_kernel");
+}
+
+// ---- events (pu_series_events; the definitions are in pulsarutils_hip.h) ----
+// Bin i of a window is above when reb[i] / sd > threshold (NaN compares false); an event is
+// a maximal run of above bins.  A workgroup owns kEvBlock consecutive bins of one row and
+// window, each wave kEvWave consecutive ones in kEvPerLane steps of 64, so bin order is
+// (workgroup, wave, step, lane).  Pass 1 counts the run starts of every workgroup, a
+// one-workgroup scan turns the counts (laid out in delivery order: row, window, workgroup)
+// into offsets, and pass 2 recomputes the starts and has each start's lane walk its run and
+// write the record at its offset: the order and the total do not depend on timing.
+
+// Run starts among the wave's 64 bins at i (one per lane): above, and the bin before not.
+// The bin before lane 0 is read from memory (the look-back across waves and workgroups).
+__device__ __forceinline__ uint64_t event_starts(const double *__restrict__ reb, int64_t nb, int64_t i, double sd,
+                                                 double thr, bool ok, int lane)
+{
+    const bool a = ok && i < nb && reb[i] / sd > thr;
+    const bool p = ok && lane == 0 && i > 0 && i < nb && reb[i - 1] / sd > thr;
+    const uint64_t am = __ballot(a);
+    const uint64_t pm = (am << 1) | (__ballot(p) & 1ull);
+    return am & ~pm;
+}
+
+__device__ __forceinline__ bool event_sd(const double *__restrict__ var, int64_t at, double *sd)
+{
+    *sd = sqrt(var[at]);
+    return *sd > 0.0 && *sd < __longlong_as_double(0x7ff0000000000000ll);  // finite and > 0 (NaN: false)
+}
+
+__global__ void __launch_bounds__(256)
+event_count_kernel(const double *__restrict__ R, int64_t nb, const double *__restrict__ var, double thr,
+                   int64_t *__restrict__ blk, int64_t per_row, int64_t first)
+{
+    __shared__ int wc[4];
+    const int64_t r = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double *reb = R + r * nb;
+    double sd;
+    const bool ok = event_sd(var, r, &sd);
+    const int64_t i0 = (int64_t)blockIdx.x * kEvBlock + (int64_t)wave * kEvWave + lane;
+    int c = 0;
+#pragma unroll
+    for (int it = 0; it < kEvPerLane; ++it) c += __popcll(event_starts(reb, nb, i0 + 64 * it, sd, thr, ok, lane));
+    if (lane == 0) wc[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) blk[r * per_row + first + blockIdx.x] = (int64_t)(wc[0] + wc[1] + wc[2] + wc[3]);
+}
+
+// In place: blk[i] (counts, m of them) -> *total + their exclusive prefix sum; *total += sum.
+// One workgroup of 1024, 8 consecutive entries per thread and step.
+__global__ void __launch_bounds__(1024) event_scan_kernel(int64_t *__restrict__ blk, int64_t m, int64_t *total)
+{
+    __shared__ int64_t wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t carry = *total;
+    __syncthreads();  // every thread has read *total before thread 0 replaces it
+    for (int64_t c0 = 0; c0 < m; c0 += 8 * 1024) {
+        const int64_t i0 = c0 + (int64_t)threadIdx.x * 8;
+        int64_t v[8], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            v[j] = i0 + j < m ? blk[i0 + j] : 0;
+            sum += v[j];
+        }
+        int64_t inc = sum;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int64_t o = __shfl_up(inc, d);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int64_t before = 0, all = 0;
+        for (int w = 0; w < 16; ++w) {
+            if (w < wave) before += wsum[w];
+            all += wsum[w];
+        }
+        int64_t run = carry + before + inc - sum;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (i0 + j < m) {
+                blk[i0 + j] = run;
+                run += v[j];
+            }
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ void __launch_bounds__(256)
+event_emit_kernel(const double *__restrict__ R, int64_t nb, int window, const double *__restrict__ var, double thr,
+                  const int64_t *__restrict__ blk, int64_t per_row, int64_t first, const int32_t *__restrict__ idx,
+                  int64_t row0, pu_event *__restrict__ events, int64_t cap)
+{
+    __shared__ int wc[4];
+    const int64_t r = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double *reb = R + r * nb;
+    double sd;
+    const bool ok = event_sd(var, r, &sd);
+    const int64_t i0 = (int64_t)blockIdx.x * kEvBlock + (int64_t)wave * kEvWave + lane;
+    uint64_t starts[kEvPerLane];
+    int c = 0;
+#pragma unroll
+    for (int it = 0; it < kEvPerLane; ++it) {
+        starts[it] = event_starts(reb, nb, i0 + 64 * it, sd, thr, ok, lane);
+        c += __popcll(starts[it]);
+    }
+    if (lane == 0) wc[wave] = c;
+    __syncthreads();
+    int64_t pos = blk[r * per_row + first + blockIdx.x];
+    for (int w = 0; w < wave; ++w) pos += wc[w];
+    const int32_t label = idx ? idx[r] : (int32_t)(row0 + r);
+#pragma unroll
+    for (int it = 0; it < kEvPerLane; ++it) {
+        const uint64_t m = starts[it];
+        const int64_t at = pos + __popcll(m & ((1ull << lane) - 1ull));
+        pos += __popcll(m);
+        if (!((m >> lane) & 1ull) || at >= cap) continue;
+        // this lane's bin starts a run: walk it (first largest bin is the peak)
+        const int64_t start = i0 + 64 * it;
+        int64_t j = start, peak = start;
+        double best = reb[start];
+        for (++j; j < nb; ++j) {
+            const double v = reb[j];
+            if (!(v / sd > thr)) break;
+            if (v > best) {
+                best = v;
+                peak = j;
+            }
+        }
+        pu_event e;
+        e.row = label;
+        e.window = window;
+        e.start = start;
+        e.nbins = j - start;
+        e.peak = peak;
+        e.snr = best / sd;
+        events[at] = e;
+    }
+}
+
+// Events of one batch of rows, appended at *w.total (device) in delivery order.
+int events_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const int32_t *idx, int64_t row0,
+                 double thr, pu_event *events, int64_t cap, void *ws, hipStream_t s)
+{
+    StatsWs w = carve(ws, rows, n, true);
+    int rc = stats_moments(plane, rows, n, ld, w, s);
+    if (rc) return rc;
+    const int64_t per_row = event_blocks(n);
+    int64_t first[4], nblk[4];
+    int64_t f = 0;
+    for (int k = 0; k < 4; ++k) {
+        nblk[k] = ((n >> k) + kEvBlock - 1) / kEvBlock;
+        first[k] = f;
+        f += nblk[k];
+    }
+    for (int k = 0; k < 4 && nblk[k]; ++k) {
+        hipLaunchKernelGGL(event_count_kernel, dim3((unsigned)nblk[k], (unsigned)rows), dim3(256), 0, s, w.R[k], n >> k,
+                           w.var + k * rows, thr, w.blk, per_row, first[k]);
+        if ((rc = pu::launch_check("event_count_kernel"))) return rc;
+    }
+    hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(1024), 0, s, w.blk, rows * per_row, w.total);
+    if ((rc = pu::launch_check("event_scan_kernel"))) return rc;
+    if (cap == 0) return PU_OK;
+    for (int k = 0; k < 4 && nblk[k]; ++k) {
+        hipLaunchKernelGGL(event_emit_kernel, dim3((unsigned)nblk[k], (unsigned)rows), dim3(256), 0, s, w.R[k], n >> k,
+                           1 << k, w.var + k * rows, thr, w.blk, per_row, first[k], idx, row0, events, cap);
+        if ((rc = pu::launch_check("event_emit_kernel"))) return rc;
+    }
+    return PU_OK;
 }
 
 }  // namespace
@@ -492,6 +704,43 @@ int pu_series_stats(const double *series, int64_t rows, int64_t n, int64_t ld, c
         if (rc) return rc;
     }
     return PU_OK;
+}
+
+size_t pu_series_events_workspace_bytes(int64_t rows, int64_t n)
+{
+    if (rows <= 0 || n <= 0) return 0;
+    return events_bytes(rows, n);
+}
+
+int pu_series_events(const double *series, int64_t rows, int64_t n, int64_t ld, const int32_t *index, double threshold,
+                     pu_event *events, int64_t cap, int64_t *count, void *workspace, size_t workspace_bytes,
+                     void *stream)
+{
+    PU_REQUIRE(series && count, "pu_series_events: NULL pointer");
+    PU_REQUIRE(rows > 0 && n > 0 && ld >= n, "pu_series_events: bad shape");
+    PU_REQUIRE(rows < (int64_t(1) << 31) && n < (int64_t(1) << 40), "pu_series_events: too large");
+    PU_REQUIRE(cap >= 0 && (events || cap == 0), "pu_series_events: cap < 0, or events NULL with cap > 0");
+    PU_REQUIRE(std::isfinite(threshold) && threshold > 0.0, "pu_series_events: threshold must be finite and > 0");
+    PU_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
+               "pu_series_events: workspace NULL or not 256-byte aligned");
+    // rows per batch: as many as the workspace holds (and a launch's grid.y)
+    int64_t per = std::min<int64_t>(rows, 32768);
+    while (per > 1 && events_bytes(per, n) > workspace_bytes) per = (per + 1) / 2;
+    PU_REQUIRE(events_bytes(per, n) <= workspace_bytes, "pu_series_events: workspace holds no row (%zu bytes)",
+               workspace_bytes);
+    hipStream_t s = pu::as_stream(stream);
+    int64_t *total = carve(workspace, per, n, true).total;  // device: events delivered so far
+    int rc = pu::hip_check(hipMemsetAsync(total, 0, sizeof(int64_t), s), "hipMemsetAsync(event total)");
+    for (int64_t r0 = 0; r0 < rows && !rc; r0 += per) {
+        const int64_t m = std::min(per, rows - r0);
+        rc = events_batch(series + r0 * ld, m, n, ld, index ? index + r0 : nullptr, r0, threshold, events, cap,
+                          workspace, s);
+    }
+    if (!rc)
+        rc = pu::hip_check(hipMemcpyAsync(count, total, sizeof(int64_t), hipMemcpyDeviceToHost, s),
+                           "hipMemcpyAsync(event count)");
+    const int rs = pu::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(events)");
+    return rc ? rc : rs;
 }
 
 }  // extern "C"

@@ -45,6 +45,8 @@ SIGNATURES = {
     "pu_nonfinite_any": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp]),
     "pu_series_stats_workspace_bytes": (_sz, [_i64, _i64]),
     "pu_series_stats": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pu_series_events_workspace_bytes": (_sz, [_i64, _i64]),
+    "pu_series_events": (_i32, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "pu_plan_info": (_i32, [_vp, _vp, _i32]),
     "pu_plan_enable_timing": (_i32, [_vp, _i32]),
     "pu_plan_kernel_times": (_i32, [_vp, _vp, _i32]),
@@ -85,6 +87,9 @@ INFO_FIELDS = ("ndm", "dm_tiles", "time_tiles", "trials_per_tile", "time_tile", 
                "row_stride", "lds_bytes", "acc_is_f64", "max_spread", "group", "slots", "stages",
                "slot_bytes", "raw_stride", "exec_adds", "lds_traffic", "cert_rechecked", "cert_nan", "cert_std", "cert_sign",
                "cert_tie", "cert_us", "kernel", "rec_elem_bytes", "rec_stride")
+# pu_event (include/pulsarutils_hip.h): 40 bytes, no padding
+EVENT_DTYPE = np.dtype([("row", "<i4"), ("window", "<i4"), ("start", "<i8"), ("nbins", "<i8"), ("peak", "<i8"),
+                        ("snr", "<f8")])
 KERNEL_NAMES = ("dedisp_kernel", "dedisp_f64_kernel", "dedisp_sub_kernel", "dedisp_sub_kernel (u16 slots)")
 
 
@@ -448,6 +453,20 @@ class Plan:
               "pu_plan_exact_series")
         return out
 
+    def events(self, data, trials, threshold, stream=None):
+        """Single-pulse events (pu_series_events, ``EVENT_DTYPE`` records on the host) of the
+        exact float64 series of the given plan trials; ``row`` is the plan trial.  Trials go
+        through ``exact_series`` + ``series_events`` in batches whose series and workspace stay
+        under about 1 GiB."""
+        tr = np.ascontiguousarray(trials, dtype=np.int32).ravel()
+        per = max(1, (1 << 30) // max(1, 24 * self.nsamples))
+        out = [np.zeros(0, EVENT_DTYPE)]
+        for b0 in range(0, tr.size, per):
+            part = tr[b0:b0 + per]
+            series = self.exact_series(data, part, stream=stream)
+            out.append(series_events(series, threshold, index=part, stream=stream))
+        return np.concatenate(out)
+
     def records(self, workspace):
         """The per-(trial, time tile) partial records at the start of ``workspace``, as a
         (ndm, time_tiles, rec_stride) float32 / float64 view (pu_plan_finalize_range)."""
@@ -571,6 +590,43 @@ def series_stats(series, stream=None):
                                 ptr(out[3]), ctypes.c_void_p(ws.data_ptr() + off), wsb, stream_ptr(stream)),
           "pu_series_stats")
     return out
+
+
+def series_events(series, threshold, index=None, stream=None):
+    """pu_series_events: the events (``EVENT_DTYPE`` numpy records, sorted by row, window,
+    start) of float64 dedispersed series (rows of a 2-D CUDA tensor) at ``threshold``;
+    ``row`` is ``index[r]`` (int32 labels, default the row number)."""
+    t = require_gpu()
+    if not (isinstance(series, t.Tensor) and series.is_cuda and series.dtype == t.float64 and series.dim() == 2
+            and series.stride(1) == 1):
+        raise ValueError("series must be a 2-D row-major float64 CUDA tensor")
+    rows, n = series.shape
+    dev = series.device
+    if rows == 0:
+        return np.zeros(0, EVENT_DTYPE)
+    idx = None
+    if index is not None:
+        ih = np.ascontiguousarray(index, dtype=np.int32).ravel()
+        if ih.size != rows:
+            raise ValueError(f"index must hold one label per row ({rows}), got {ih.size}")
+        idx = t.from_numpy(ih).to(dev)
+    per = max(1, min(rows, (1 << 30) // max(1, 16 * n)))
+    wsb = lib().pu_series_events_workspace_bytes(per, n)
+    ws = t.empty(wsb + 256, dtype=t.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    cap = max(256, 8 * rows)
+    count = ctypes.c_int64(0)
+    while True:
+        buf = t.empty(cap * EVENT_DTYPE.itemsize, dtype=t.uint8, device=dev)
+        check(lib().pu_series_events(ptr(series), rows, n, series.stride(0), ptr(idx), float(threshold), ptr(buf), cap,
+                                     ctypes.byref(count), ctypes.c_void_p(ws.data_ptr() + off), wsb,
+                                     stream_ptr(stream)), "pu_series_events")
+        if count.value <= cap:
+            break
+        cap = count.value  # more events than room: once more with room for all
+    if count.value == 0:
+        return np.zeros(0, EVENT_DTYPE)
+    return buf[:count.value * EVENT_DTYPE.itemsize].cpu().numpy().view(EVENT_DTYPE).copy()
 
 
 class MaskedStream:

@@ -525,7 +525,7 @@ def dm_broadening(dm, freq, df):
 
 def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmmin=200, dmmax=800, surelybad=[],
                      save_candidates=True, snr_threshold=6, acc=None, search_dtype="f64", profile=None,
-                     zero_dm=False):
+                     zero_dm=False, find_pulses=False, pulse_threshold=None, dm_tol=2, time_tol=0):
     """clean.py:276-351: stream a SIGPROC file through clean + DM search, chunk by chunk.
 
     Same chunking as the reference: ``step = max(int(chunk_length / tsamp) * 2, 128)``
@@ -552,6 +552,17 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
     each candidate's PulseInfo is pickled to ``{root}_{istart}-{iend}.pkl`` like the
     reference; the diagnostic plots (``plot_diagnostics``, matplotlib + hendrics H-test)
     are out of scope and not drawn.
+
+    ``find_pulses=True`` answers what those plots were for: each candidate gains
+    ``'pulses'``, the table of :func:`pulsarutils.pulses.find_pulses` (one row per single
+    pulse: DM, time, width, S/N, extent, ``wrapped``) computed on the array that was searched
+    (its float32 cast with ``search_dtype="f32"``) at ``pulse_threshold`` (default
+    ``snr_threshold``) with ``dm_tol`` / ``time_tol``; ``time`` is offset by the chunk's
+    ``t0`` and a column ``file_sample = istart + N * sample`` is added.  Pulses are NOT merged
+    across chunks: the 50 % overlap exists so that every pulse is unwrapped in one chunk, and
+    a pulse seen in two overlapping chunks is listed in both - ``wrapped`` tells the caller
+    which listing read across the chunk's circular seam, i.e. which one to drop.  With the
+    default ``False`` nothing changes: no new key, the same calls, the same pickles.
     """
     import os
     import pickle
@@ -668,12 +679,22 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
             rec = {"istart": istart, "nsamples": chunk_size, "ndm": int(trial_DMs.size)}
             rec.update({name: (tt - marks[i][1]) * 1e3 for i, (name, tt) in enumerate(marks[1:])})
             profile.append(rec)
+        outs = (mx, sd, snr, win)
         snr = _host(snr)
         table = make_table({'DM': trial_DMs, 'max': _host(mx), 'std': _host(sd), 'snr': snr, 'rebin': _host(win)})
         if np.any(snr > snr_threshold):
             best = int(np.argmax(snr))
             cand = {'istart': istart, 'iend': iend, 't0': t0, 'dm': float(trial_DMs[best]),
                     'snr': float(snr[best]), 'rebin': int(table['rebin'][best]), 'table': table}
+            if find_pulses:
+                from .pulses import find_pulses as _find_pulses
+                pulses = _find_pulses(array, trial_DMs, nchan, start_freq, bandwidth, new_sample_time,
+                                      threshold=snr_threshold if pulse_threshold is None else pulse_threshold,
+                                      acc=acc, dm_tol=dm_tol, time_tol=time_tol, plan=plan, table=outs)
+                cols = {c: pulses[c] for c in pulses.colnames}
+                cols['time'] = cols['time'] + t0
+                cols['file_sample'] = istart + N * np.asarray(cols['sample'], dtype=np.int64)
+                cand['pulses'] = make_table(cols)
             candidates.append(cand)
             if save_candidates:
                 info = PulseInfo()

@@ -255,6 +255,25 @@ def dedispersion_search(data, dmmin, dmmax, start_freq, bandwidth, sample_time, 
     return table, _numpy_out(plane).astype(np.float64, copy=False)
 
 
+def single_pulse_search(data, dmmin, dmmax, start_freq, bandwidth, sample_time, threshold=6.0, acc=None, dm_tol=2,
+                        time_tol=0):
+    """``dedispersion_search(..., show=False)`` plus the single pulses of the chunk:
+    returns ``(table, pulses)``, ``table`` exactly that search's table and ``pulses`` the
+    table of :func:`pulsarutils.pulses.find_pulses` (DM, time, width, S/N per pulse) from the
+    same search's outputs.  The reference has no counterpart: it draws ``plot_diagnostics``
+    and a person reads the pulses off the plot."""
+    from .pulses import find_pulses
+    nchan = data.shape[0]
+    trial_DMs = dedispersion_plan(nchan, dmmin, dmmax, start_freq, bandwidth, sample_time)
+    x = _prepare_data(data)
+    outs, plan = search_device(x, trial_DMs, nchan, start_freq, bandwidth, sample_time, acc=acc)
+    mx, sd, snr, win = (_numpy_out(o) for o in outs)
+    table = make_table({"DM": trial_DMs, "max": mx, "std": sd, "snr": snr, "rebin": win})
+    pulses = find_pulses(x, trial_DMs, nchan, start_freq, bandwidth, sample_time, threshold=threshold, acc=acc,
+                         dm_tol=dm_tol, time_tol=time_tol, plan=plan, table=outs)
+    return table, pulses
+
+
 def apply_dm_shifts_to_data(data, shifts):
     """dedispersion.py:254-258: roll channel i by ``-rint(shifts[i])`` (input dtype kept).
 
