@@ -802,8 +802,12 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
     // the allocation returns 0 (clamping them costs a VALU add per read - the reads then
     // cannot fold 256 u into the ds_read offset field - and was measured 1.8 ms slower at
     // C2, 20.2 vs 18.4 ms).
-    auto build_pass = [&](auto upc, const meta_t &m, int gs, int i0, int lim, bool whole, int copy_bytes) {
+    // A pass of a width matched to the slot (exact: all its chunks < lim, see slot()) has no
+    // guarded store path at all.
+    auto build_pass = [&](auto upc, auto exact, const meta_t &m, int gs, int i0, int lim, bool whole_cb,
+                          int copy_bytes) {
         constexpr int UP = decltype(upc)::value;
+        const bool whole = decltype(exact)::value || whole_cb;
         auto at = [&](int u) { return i0 + 64 * u + lane; };
         float r[UP];
         if constexpr (kDma && EB == 1) {
@@ -1041,13 +1045,31 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
         // Every slot has a first pass (len >= TT): peeled, with the tile's whole0.
         // Two slots per iteration with ping-pong records (rotating one record through a copy
         // cost a dozen scalar moves per slot).
+        // The first pass is U chunks wide or, for a slot that needs fewer, UN = U - 1 (picked
+        // by a wave-uniform test on lim): a fixed U read, summed and stored a chunk no window
+        // reads, past lim, into the copy's padding - 73 % of C2's slots, nearly all of C5's
+        // and all of C4's.  len > TT, so lim >= 64 UN: neither first pass
+        // runs past lim, both end inside the copy (4 lim <= copy_bytes) and store without
+        // guards.  Plans whose U is already the shortest slot's chunk count (UN = U: G = 8,
+        // float64 G >= 4) keep the one first pass.  Trailing passes are full-width, guarded
+        // where they end past the copy (C2: 40 of 5109 slots have one; a 1-chunk pass for
+        // them cost the wide float G = 4 kernel register spills).
+        constexpr int UN = TT / 64 + 1 < U ? U - 1 : U;
         auto slot = [&](const meta_t &m) {
             const int len = m[0], gs = m[3];
             const int lim = (len + 63) & ~63;
             const int cb = copy_bytes_of(len);
-            build_pass(std::integral_constant<int, U>{}, m, gs, 0, lim, pass_whole(0, cb), cb);
+            if constexpr (UN < U) {
+                if (lim < 64 * U)
+                    build_pass(std::integral_constant<int, UN>{}, std::true_type{}, m, gs, 0, lim, true, cb);
+                else
+                    build_pass(std::integral_constant<int, U>{}, std::true_type{}, m, gs, 0, lim, true, cb);
+            } else {
+                build_pass(std::integral_constant<int, U>{}, std::false_type{}, m, gs, 0, lim, pass_whole(0, cb), cb);
+            }
             for (int i0 = 64 * U; i0 < len; i0 += 64 * U)
-                build_pass(std::integral_constant<int, U>{}, m, gs, i0, lim, pass_whole(i0, cb), cb);
+                build_pass(std::integral_constant<int, U>{}, std::false_type{}, m, gs, i0, lim, pass_whole(i0, cb),
+                           cb);
         };
         meta_t ma = m0;
         const meta_t *mp = reinterpret_cast<const meta_t *>(slots) + (size_t)(st.z + wave + W);
