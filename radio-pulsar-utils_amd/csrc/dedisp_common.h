@@ -1,8 +1,9 @@
 // Device helpers shared by the dedispersion translation units (dedisperse.hip: the
-// float32-accumulation and channel-mode kernels, the planner and the C-ABI;
-// dedisp_f64.hip: the float64 prefetching kernel, compiled with its own code-generation
-// options).  Everything here is in an anonymous namespace: each translation unit gets its
-// own copy of these inline functions and templates.
+// float32-accumulation and channel-mode kernels and the C-ABI; dedisp_f64.hip: the float64
+// prefetching kernel, compiled with its own code-generation options).  Everything here is
+// in an anonymous namespace: each translation unit gets its own copy of these inline
+// functions and templates.  The geometry constants the host planner shares (kWaves, kD,
+// kTPT, ...) are in dedisp_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,18 +11,10 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "dedisp_plan.h"
 #include "pu_common.h"
 
 namespace {
-
-constexpr int kWaves = 8;                 // waves per workgroup (each owns D trials): 2 WGs = 4 waves/SIMD
-constexpr int kThreads = kWaves * 64;
-constexpr int kD = 8;                     // trials per wave
-constexpr int kTPT = kWaves * kD;         // trials per tile
-constexpr int kPartStride = 16;           // elements per (trial, time tile) partial record: the
-                                          // accumulation type's (float: 64 B, double: 128 B)
-constexpr size_t kLdsBudget = 64 * 1024;  // per workgroup: 2 workgroups / CU
-constexpr int kMaxSpread = 2048;
 
 struct DedispArgs {
     const void *data;

@@ -315,7 +315,7 @@ dedisp_f64_kernel(DedispArgs a, const int32_t *__restrict__ tile_first, const in
     write_outputs<double, double, K, D, PLANE, STATS>(acc, a, first, slot0, cnt, t0, tt, lane);
 }
 
-// the production shape: 16 waves x 4 trials (kF64Waves in dedisperse.hip's planner)
+// the production shape: 16 waves x 4 trials (the planner's kF64Waves, dedisp_plan.h)
 constexpr int kF64W = 16, kF64D = 4;
 
 template <typename Tin>

@@ -1,7 +1,9 @@
 // Stand-alone run of the host planner (pu_shift_table + pu_plan_describe) over small cases
-// of every planning path, for `make sanitize-plan`: the library's own planner sources built
-// with AddressSanitizer and UBSan on the host side, run on a machine without a GPU.  Prints
-// each case's plan and table digest; exits non-zero if a case fails to plan.
+// of every planning path: linked with the library's own planner objects (planner.o, plan.o)
+// and no HIP library - `make plan_check`; the sources under AddressSanitizer and UBSan -
+// `make sanitize-plan`.  Prints each case's plan and table digest; exits non-zero if a case
+// fails to plan.  A case named like a key of tests/golden/plan_tables.json is that case
+// (tests/test_planner.py compares the digests).
 #include <algorithm>
 #include <cinttypes>
 #include <cstdio>
@@ -31,11 +33,13 @@ void run(const char *name, int dtype, int acc, int64_t nchan, int64_t n, const s
                 name, info[23], info[10], info[1], info[12], info[7], digest);
 }
 
-// the reference's shifts for ``ndm`` trials in [0, 50] pc cm^-3, 400-500 MHz, 1 ms samples
+// the reference's shifts for numpy.linspace(0, 50, ndm) pc cm^-3, 400-500 MHz, 1 ms samples
 std::vector<int64_t> grid(int64_t nchan, int64_t ndm = 40)
 {
     std::vector<double> dms((size_t)ndm);
-    for (int64_t d = 0; d < ndm; ++d) dms[(size_t)d] = 50.0 * (double)d / (double)(ndm - 1);
+    const double step = 50.0 / (double)(ndm - 1);
+    for (int64_t d = 0; d < ndm; ++d) dms[(size_t)d] = (double)d * step;
+    dms[(size_t)(ndm - 1)] = 50.0;
     std::vector<int64_t> sh((size_t)(ndm * nchan));
     if (pu_shift_table(nchan, dms.data(), ndm, 400.0, 100.0, 1e-3, sh.data()) != PU_OK) {
         std::printf("pu_shift_table failed: %s\n", pu_last_error());
@@ -78,28 +82,28 @@ int main()
     for (int g : {0, 2, 4, 8})
         for (int s16 : {-1, 0}) {
             char name[64];
-            std::snprintf(name, sizeof name, "u8 tall g%d slot16 %d", g, s16);
+            std::snprintf(name, sizeof name, "u8_tall_g%d_slot16_%s", g, s16 < 0 ? "None" : "False");
             run(name, PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts(g, 2, 0, -1, -1, s16));
         }
-    run("u8 pair g4", PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts(4, 1));
+    run("u8_pair_g4", PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts(4, 1));
     run("u8 wide g8", PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts(8, 0));
     run("u8 default", PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts());
-    run("u8 n 4099", PU_U8, PU_ACC_NATIVE, 64, 4099, g64, opts());
-    run("u8 n 4099 tall g4", PU_U8, PU_ACC_NATIVE, 64, 4099, g64, opts(4, 2));
-    run("u8 no dma tall g4", PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts(4, 2, 0, 0));
-    run("u8 acc f64", PU_U8, PU_ACC_F64, 64, 4096, g64, opts());
+    run("u8_n4099", PU_U8, PU_ACC_NATIVE, 64, 4099, g64, opts());
+    run("u8_n4099_tall_g4", PU_U8, PU_ACC_NATIVE, 64, 4099, g64, opts(4, 2));
+    run("u8_no_dma_tall_g4", PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts(4, 2, 0, 0));
+    run("u8_acc_f64", PU_U8, PU_ACC_F64, 64, 4096, g64, opts());
     run("f32 default", PU_F32, PU_ACC_NATIVE, 64, 4096, g64, opts());
-    run("f32 channel mode", PU_F32, PU_ACC_NATIVE, 64, 4096, g64, opts(1));
+    run("f32_channel_mode", PU_F32, PU_ACC_NATIVE, 64, 4096, g64, opts(1));
     run("f32 acc f64", PU_F32, PU_ACC_F64, 64, 4096, g64, opts());
     run("f64", PU_F64, PU_ACC_NATIVE, 64, 4096, g64, opts());
-    run("f64 acc f32 g4", PU_F64, PU_ACC_F32, 64, 4096, g64, opts(4));
-    run("u8 nchan 50 g4", PU_U8, PU_ACC_NATIVE, 50, 4096, g50, opts(4));
-    run("f32 nchan 50 g4", PU_F32, PU_ACC_NATIVE, 50, 4096, g50, opts(4));
+    run("f64_acc_f32_g4", PU_F64, PU_ACC_F32, 64, 4096, g64, opts(4));
+    run("u8_nchan50_g4", PU_U8, PU_ACC_NATIVE, 50, 4096, g50, opts(4));
+    run("f32_nchan50_g4", PU_F32, PU_ACC_NATIVE, 50, 4096, g50, opts(4));
     for (int kb : {64, 8}) {
         char name[64];
-        std::snprintf(name, sizeof name, "u8 tall g4 lds %d", kb);
+        std::snprintf(name, sizeof name, "u8_tall_g4_lds%d", kb);
         run(name, PU_U8, PU_ACC_NATIVE, 64, 4096, g64, opts(4, 2, kb));
-        std::snprintf(name, sizeof name, "f32 lds %d", kb);
+        std::snprintf(name, sizeof name, "f32_lds%d", kb);
         run(name, PU_F32, PU_ACC_NATIVE, 64, 4096, g64, opts(0, -1, kb));
     }
     run("u8 wrapping", PU_U8, PU_ACC_NATIVE, 48, 1024, wrap, opts(4, 2));
@@ -110,13 +114,13 @@ int main()
         char name[64];
         std::snprintf(name, sizeof name, "u8 wrapping dt_major %d", dtm);  // 50 DM tiles to order
         run(name, PU_U8, PU_ACC_NATIVE, 48, 1024, wrap, opts(4, 2, 0, -1, dtm));
-        std::snprintf(name, sizeof name, "f32 lds 64 dt_major %d", dtm);  // 4 DM tiles
+        std::snprintf(name, sizeof name, "f32_lds64_dt_major_%s", dtm ? "True" : "False");  // 4 DM tiles
         run(name, PU_F32, PU_ACC_NATIVE, 64, 4096, g64, opts(0, -1, 64, -1, dtm));
     }
-    run("f32 nchan 3", PU_F32, PU_ACC_NATIVE, 3, 4096, g3, opts());
-    run("u8 nchan 3", PU_U8, PU_ACC_NATIVE, 3, 4096, g3, opts());
-    run("f32 nchan 1", PU_F32, PU_ACC_NATIVE, 1, 4096, g1, opts());
-    run("u8 nchan 1", PU_U8, PU_ACC_NATIVE, 1, 4096, g1, opts());
+    run("f32_nchan3", PU_F32, PU_ACC_NATIVE, 3, 4096, g3, opts());
+    run("u8_nchan3", PU_U8, PU_ACC_NATIVE, 3, 4096, g3, opts());
+    run("f32_nchan1", PU_F32, PU_ACC_NATIVE, 1, 4096, g1, opts());
+    run("u8_nchan1", PU_U8, PU_ACC_NATIVE, 1, 4096, g1, opts());
     std::printf("%d case(s) failed\n", failures);
     return failures ? 1 : 0;
 }

@@ -1,4 +1,5 @@
-// Shared host/device helpers for libpulsarutils_hip (gfx950).
+// Shared host/device helpers for libpulsarutils_hip (gfx950).  What needs no HIP
+// (set_error, PU_REQUIRE, elem_size, the tuning knobs) is in pu_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,11 +8,10 @@
 #include <cstdlib>
 #include <string>
 
+#include "pu_host.h"
 #include "pulsarutils_hip.h"
 
 namespace pu {
-
-void set_error(const char *fmt, ...);
 
 // Map a HIP status to PU_EHIP with a message; returns PU_OK on success.
 inline int hip_check(hipError_t e, const char *what)
@@ -27,14 +27,6 @@ inline int hip_check(hipError_t e, const char *what)
         if (_rc != PU_OK) return _rc;                     \
     } while (0)
 
-#define PU_REQUIRE(cond, ...)                             \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            ::pu::set_error(__VA_ARGS__);                 \
-            return PU_EINVAL;                             \
-        }                                                 \
-    } while (0)
-
 // Launch-error check after a kernel launch.
 inline int launch_check(const char *name)
 {
@@ -42,41 +34,6 @@ inline int launch_check(const char *name)
     if (e == hipSuccess) return PU_OK;
     set_error("launch %s: %s", name, hipGetErrorString(e));
     return PU_EHIP;
-}
-
-inline size_t elem_size(int dtype)
-{
-    switch (dtype) {
-    case PU_U8: return 1;
-    case PU_F32: return 4;
-    case PU_F64: return 8;
-    case PU_I64: return 8;
-    default: return 0;
-    }
-}
-
-// Tuning knobs for A/B experiments (group size, workgroup shape, batch sizes ...): read
-// from the environment ONLY in the diagnostic build (make stamps: -DPU_STAMPS,
-// libpulsarutils_hip_stamps.so).  The production library ignores the environment and
-// always runs its defaults or the explicit plan-create arguments, so a stray PU_* in a
-// user's environment cannot change a kernel (the reference is configured by kwargs only).
-inline bool knob_set(const char *name)
-{
-#ifdef PU_STAMPS
-    return getenv(name) != nullptr;
-#else
-    (void)name;
-    return false;
-#endif
-}
-
-inline int knob(const char *name, int dflt)
-{
-#ifdef PU_STAMPS
-    if (const char *e = getenv(name)) return atoi(e);
-#endif
-    (void)name;
-    return dflt;
 }
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
