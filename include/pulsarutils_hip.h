@@ -483,6 +483,56 @@ int pu_quantize_pack_transpose(const void *src, int dtype, int64_t nchans, int64
                                const double *scale, const double *offset, int nbits,
                                void *dst, int64_t ld_dst, void *stream);
 
+/* ------------------------------------------------------------------ folding / H-test */
+
+/* Fold a chunk at a pulse period.  No reference counterpart: the reference's PulseInfo
+ * (clean.py:27-55) and its dedispersion_search (clean.py:136-180, sample_time = 1 / pulse_freq
+ * / nbin) take a folded profile, and nothing in it makes one from a filterbank.
+ * x: device, nchan rows of ld elements (PU_U8 / PU_F32 / PU_F64).  Sample t (0 <= t < n) falls
+ * in bin b(t), every step one IEEE float64 operation and no fused multiply-add:
+ *     p = phase0 + (double)(first_sample + t) * dphase
+ *     f = p - floor(p)
+ *     b = min((int64)(f * (double)nbin), nbin - 1)
+ * (numpy's elementwise phase0 + idx.astype(float64) * dphase gives the same bits, bin edges
+ * included).  The call ACCUMULATES: sums[c * ld_sums + b] += the sum of (double)x[c][t] over
+ * the t with b(t) = b, counts[b] += their number (device; the caller zeroes both before the
+ * first chunk; first_sample = the chunk's position in the file, so the folds of the chunks
+ * add up to the fold of the file).  Arithmetic: no floating-point atomics; the order of every
+ * sum is fixed by the arguments (segments of 16384 samples from the chunk's start, groups of
+ * 64 samples inside them; the per-segment partials are added in segment order, then to
+ * sums), so equal calls give equal bits on any device and launch shape.  Exact for PU_U8 and
+ * whenever the values and partial sums are integers below 2^53; otherwise each call's
+ * addend is within m 2^-53 sum|x| of the exact sum of the bin's m samples.
+ * PU_EINVAL: nbin < 1, n < 0, ld < n, ld_sums < nbin, a non-finite phase0 / dphase, |p| >=
+ * 2^52 at either end of the chunk, a workspace smaller than pu_fold_workspace_bytes(nchan, n,
+ * nbin) or not 8-byte aligned.  PU_EUNSUPPORTED: nbin > 8192 (a channel tile's bins are LDS
+ * accumulators; there is no slower path).  PU_OK without a launch for n == 0 or nchan == 0.
+ * All checked before any HIP call; asynchronous on stream. */
+size_t pu_fold_workspace_bytes(int64_t nchan, int64_t n, int64_t nbin);
+int pu_fold(const void *x, int dtype, int64_t nchan, int64_t n, int64_t ld, int64_t first_sample,
+            double phase0, double dphase, int64_t nbin, double *sums, int64_t ld_sums,
+            int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The binned Z^2_n and H-test (de Jager et al. 1989) of float64 profiles, in the form of
+ * hendrics' / stingray's h_test, which plot_diagnostics calls on every DM row (clean.py:252-253;
+ * hendrics itself is no dependency here, so this definition is the project's).  For each row
+ * p[0 .. n) of profiles (device, rows x n, leading dimension ld):
+ *     P     = sum_j p[j]
+ *     C_k   = sum_j p[j] cos(2 pi r / n),  S_k = sum_j p[j] sin(2 pi r / n),  r = (k j) mod n
+ *     Z^2_m = (2 / P) sum_{k = 1 .. m} (C_k^2 + S_k^2),   m = 1 .. nmax
+ *     H     = max_m (Z^2_m - 4 m + 4),   M = the first m that attains it
+ * with r an exact integer, the phases from a table of n sincospi values and the sum over k
+ * accumulated sequentially.  h[rows], m[rows] (device); zs (device, may be NULL): Z^2_1 ..
+ * Z^2_nmax per row, leading dimension ld_zs.  A row with a non-finite value or with P not > 0
+ * gets H = NaN, M = 0 and NaN in zs.  2 <= n <= 8192 and 1 <= nmax <= n - 1 (PU_EINVAL);
+ * n > 8192 is PU_EUNSUPPORTED: the H curve of an unfolded chunk (n ~ 1e5, nmax = n / 10) needs
+ * an FFT, which this library does not have.  workspace: pu_h_test_workspace_bytes(rows, n,
+ * nmax), 16-byte aligned.  All checked before any HIP call; asynchronous on stream. */
+size_t pu_h_test_workspace_bytes(int64_t rows, int64_t n, int64_t nmax);
+int pu_h_test(const double *profiles, int64_t rows, int64_t n, int64_t ld, int64_t nmax, double *h,
+              int32_t *m, double *zs, int64_t ld_zs, void *workspace, size_t workspace_bytes,
+              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

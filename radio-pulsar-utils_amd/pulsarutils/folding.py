@@ -1,0 +1,312 @@
+"""Folding at a pulse period and the Z^2_n / H statistics: the periodic-pulsar path.
+
+``clean.PulseInfo`` and ``clean.dedispersion_search(info, dmmin, dmmax)`` are the API of a
+*folded* profile (one turn in ``nbin`` bins, ``sample_time = 1 / pulse_freq / nbin``), and
+``clean.digitize`` exists to feed the H-test of the reference's ``plot_diagnostics``
+(clean.py:252-253).  The reference makes no folded profile and draws its H-versus-DM panel
+with hendrics; this module makes the profile from a filterbank (:func:`fold`,
+:func:`fold_file`) and returns what the panel plotted as arrays (:func:`h_curve`,
+:func:`profile_stats`).  The plots themselves stay out of scope.
+
+**The bin rule** (:func:`fold_bins`; ``pu_fold`` in include/pulsarutils_hip.h computes the
+same bits on the device).  With ``dphase = sample_time * pulse_freq`` (one float64 product),
+sample ``i`` of the file falls in bin::
+
+    p = ph0 + float64(i) * dphase          # one multiply, one add, no fused multiply-add
+    f = p - floor(p)
+    b = min(int64(f * float64(nbin)), nbin - 1)
+
+**Z^2_n and H** (de Jager et al. 1989, binned as hendrics / stingray do; ``pu_h_test``).  For a
+profile ``p[0 .. n)``: ``P = sum p``, ``C_k, S_k = sum_j p[j] cos, sin(2 pi ((k j) mod n) / n)``,
+``Z^2_m = (2 / P) sum_{k <= m} (C_k^2 + S_k^2)``, ``H = max_m (Z^2_m - 4 m + 4)`` and ``M`` the
+first ``m`` that attains it.  A profile with a non-finite value or ``P`` not ``> 0`` gives NaN
+(``M = 0``).
+
+Conventions are the package's: numpy in -> numpy out, CUDA tensor in -> tensors out.
+Importable without a GPU (:func:`fold_bins` is pure numpy); everything else runs HIP kernels
+and raises ``HipBackendError`` without the library or a GPU.
+"""
+import numpy as np
+
+from . import _hip
+
+
+def fold_bins(nsamples, pulse_freq, sample_time, nbin, ph0=0.0, first_sample=0):
+    """The bin (int64) of samples ``first_sample .. first_sample + nsamples - 1``: the
+    documented definition of the fold, in numpy."""
+    nbin = int(nbin)
+    if nbin < 1:
+        raise ValueError("fold_bins: nbin must be >= 1")
+    dphase = float(sample_time) * float(pulse_freq)
+    idx = np.arange(int(first_sample), int(first_sample) + int(nsamples), dtype=np.int64)
+    prod = idx.astype(np.float64) * dphase
+    p = float(ph0) + prod
+    f = p - np.floor(p)
+    return np.minimum((f * float(nbin)).astype(np.int64), nbin - 1)
+
+
+def _fold_device(x, dphase, nbin, ph0, first_sample, sums, counts):
+    """pu_fold of a 2-D row-major device tensor into device ``sums`` / ``counts``."""
+    t = _hip.torch()
+    lib = _hip.lib()
+    nchan, n = x.shape
+    ld = x.stride(0) if nchan > 1 else max(x.stride(0), n)
+    wsb = lib.pu_fold_workspace_bytes(nchan, n, nbin)
+    ws = t.empty(max(16, wsb), dtype=t.uint8, device=x.device)
+    _hip.check(lib.pu_fold(_hip.ptr(x), _hip.dtype_code(x.dtype), nchan, n, ld, int(first_sample), float(ph0),
+                           float(dphase), int(nbin), _hip.ptr(sums), sums.stride(0), _hip.ptr(counts), _hip.ptr(ws),
+                           ws.numel(), _hip.stream_ptr()), "pu_fold")
+
+
+def fold(data, pulse_freq, sample_time, nbin, ph0=0.0, first_sample=0, out=None):
+    """Fold ``data`` (nchan, nsamples; a 1-D array is one channel) at ``pulse_freq``.
+
+    Returns ``(sums, counts)``: float64 ``(nchan, nbin)`` sums of the samples of each bin and
+    the int64 number of samples per bin (the same for every channel).  ``first_sample`` is
+    the position of ``data``'s first sample in the series the phase counts from, so chunks of
+    a file fold to partial results that add up.  ``out=(sums, counts)``: existing device
+    tensors (float64 ``(nchan, nbin)`` row-major, int64 ``(nbin,)``) to accumulate into; they
+    are returned.  uint8, float32 and float64 data are folded as they are, other types as
+    float64.  Exact for uint8 (and for integer-valued input below 2^53); reproducible bit for
+    bit otherwise (no floating-point atomics)."""
+    t = _hip.require_gpu()
+    as_numpy = not isinstance(data, t.Tensor)
+    x = _hip.to_device(data)
+    one_d = x.dim() == 1
+    if one_d:
+        x = x.reshape(1, -1)
+    if x.dim() != 2:
+        raise ValueError("fold: data must be (nchan, nsamples) or 1-D")
+    nbin = int(nbin)
+    if nbin < 1:
+        raise ValueError("fold: nbin must be >= 1")
+    nchan = x.shape[0]
+    if out is None:
+        sums = t.zeros((nchan, nbin), dtype=t.float64, device=x.device)
+        counts = t.zeros(nbin, dtype=t.int64, device=x.device)
+    else:
+        sums, counts = out
+        ok = (isinstance(sums, t.Tensor) and isinstance(counts, t.Tensor) and sums.dtype == t.float64
+              and counts.dtype == t.int64 and tuple(sums.shape) == (nchan, nbin) and tuple(counts.shape) == (nbin,)
+              and sums.stride(1) == 1 and counts.is_contiguous() and sums.device == x.device
+              and counts.device == x.device)
+        if not ok:
+            raise ValueError(f"fold: out must be a row-major float64 ({nchan}, {nbin}) tensor and a contiguous int64 "
+                             f"({nbin},) tensor on {x.device}")
+    _fold_device(x, float(sample_time) * float(pulse_freq), nbin, ph0, first_sample, sums, counts)
+    if out is not None:
+        return sums, counts
+    if one_d:
+        sums = sums[0]
+    if as_numpy:
+        return sums.cpu().numpy(), counts.cpu().numpy()
+    return sums, counts
+
+
+def fold_file(fname, pulse_freq, nbin=128, ph0=0.0, chunksize=2**17, clean=True, surelybad=(), tmin=0.0, tmax=None,
+              zero_dm=False):
+    """Fold a SIGPROC filterbank at ``pulse_freq`` (Hz) into a ``clean.PulseInfo``.
+
+    The file is streamed in non-overlapping chunks of ``chunksize`` samples (a tail shorter
+    than ``chunksize // 2`` is merged into the chunk before it); chunk k + 1 is uploaded by a
+    loader thread on a copy stream while chunk k is folded.  All array work stays in HBM;
+    1-, 2- and 4-bit files are uploaded packed and unpacked on the device
+    (``FilReader.device_block``).  The phase counts from the file's first sample, whatever
+    ``tmin``; samples ``i`` with ``tmin <= i * tsamp < tmax`` are folded.
+
+    ``clean=True``: each chunk goes through ``renormalize_device`` with the
+    ``get_bad_chans`` (+ ``surelybad``) mask, as in ``search_by_chunks`` (``zero_dm`` is its
+    opt-in subtraction), and the float64 result is folded.  ``clean=False``: the raw samples
+    are folded (exactly, for 8-bit and packed files) and the masked channels' rows are zeroed
+    at the end.
+
+    The result has ``allprofs = sums / counts`` (float64 ``(nchan, nbin)``; a bin no sample
+    hit is 0), flipped when ``foff < 0`` so that channel 0 is the lowest frequency, and
+    ``nbin, nchan, pulse_freq, ph0, start_freq, bandwidth, date`` set, plus the attribute
+    ``counts``; it feeds ``clean.dedispersion_search(info, dmmin, dmmax)`` as it is."""
+    from .clean import PulseInfo, renormalize_device
+    from .sigproc import FilReader
+    from .stats import get_bad_chans
+    nbin, chunksize = int(nbin), int(chunksize)
+    if nbin < 1 or chunksize < 1:
+        raise ValueError("fold_file: nbin and chunksize must be positive")
+    t = _hip.require_gpu()
+    mask = np.array(get_bad_chans(fname), dtype=bool)
+    for bad_chan in surelybad:
+        mask[bad_chan] = True
+    fil = FilReader(fname)
+    header = fil.header
+    nsamples, tsamp, nchan = header["nsamples"], header["tsamp"], header["nchans"]
+    i0 = min(nsamples, max(0, int(np.ceil(float(tmin) / tsamp))))
+    i1 = nsamples if tmax is None else min(nsamples, max(i0, int(np.ceil(float(tmax) / tsamp))))
+    chunks = [(i, min(chunksize, i1 - i)) for i in range(i0, i1, chunksize)]
+    if len(chunks) > 1 and chunks[-1][1] < chunksize // 2:
+        last = chunks.pop()
+        chunks[-1] = (chunks[-1][0], chunks[-1][1] + last[1])
+    dev = t.device("cuda", t.cuda.current_device())
+    dphase = float(tsamp) * float(pulse_freq)
+    sums = t.zeros((nchan, nbin), dtype=t.float64, device=dev)
+    counts = t.zeros(nbin, dtype=t.int64, device=dev)
+    overlap = len(chunks) > 1
+    copy_stream = t.cuda.Stream(device=dev) if overlap else None
+
+    def load(k):
+        istart, size = chunks[k]
+        tc = np.ascontiguousarray(fil._block_tc(istart, size))
+        with t.cuda.device(dev), t.cuda.stream(copy_stream):
+            dst = t.from_numpy(tc).to(dev)
+            ev = t.cuda.Event()
+            ev.record(copy_stream)
+        return dst, ev
+
+    pool = None
+    try:
+        if overlap:
+            from concurrent.futures import ThreadPoolExecutor
+            pool = ThreadPoolExecutor(max_workers=1)
+            pending = pool.submit(load, 0)
+        for k, (istart, size) in enumerate(chunks):
+            if overlap:
+                src, ev = pending.result()
+                if k + 1 < len(chunks):
+                    pending = pool.submit(load, k + 1)
+                t.cuda.current_stream(dev).wait_event(ev)
+                src.record_stream(t.cuda.current_stream(dev))
+            else:
+                src = t.from_numpy(np.ascontiguousarray(fil._block_tc(istart, size))).to(dev)
+            block = fil.device_block(src)
+            del src
+            if _hip.dtype_code(block.dtype) not in (_hip.PU_U8, _hip.PU_F32, _hip.PU_F64):
+                block = block.to(t.float64)
+            if clean:
+                block, _ = renormalize_device(block, badchans_mask=mask, zero_dm=zero_dm)
+            _fold_device(block, dphase, nbin, ph0, istart, sums, counts)
+            del block
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True)
+    s, c = sums.cpu().numpy(), counts.cpu().numpy()
+    allprofs = np.zeros_like(s)
+    hit = c > 0
+    allprofs[:, hit] = s[:, hit] / c[hit].astype(np.float64)
+    allprofs[mask] = 0.0
+    if header["foff"] < 0:
+        allprofs = np.ascontiguousarray(allprofs[::-1])
+    info = PulseInfo()
+    info.allprofs = allprofs
+    info.counts = c
+    info.nbin = nbin
+    info.nchan = nchan
+    info.pulse_freq = float(pulse_freq)
+    info.ph0 = float(ph0)
+    info.start_freq = header["fbottom"]
+    info.bandwidth = header["bandwidth"]
+    info.date = header.get("tstart")
+    return info
+
+
+def _h_test_device(prof, nmax, want_zs):
+    """pu_h_test of a 2-D row-major float64 device tensor -> (h, m, zs or None) tensors."""
+    t = _hip.torch()
+    lib = _hip.lib()
+    rows, n = prof.shape
+    nmax = int(nmax)
+    h = t.empty(rows, dtype=t.float64, device=prof.device)
+    m = t.empty(rows, dtype=t.int32, device=prof.device)
+    zs = t.empty((rows, max(nmax, 1)), dtype=t.float64, device=prof.device) if want_zs else None
+    wsb = lib.pu_h_test_workspace_bytes(rows, n, nmax)
+    ws = t.empty(max(16, wsb), dtype=t.uint8, device=prof.device)  # (allocator blocks are 512-byte aligned)
+    ld = prof.stride(0) if rows > 1 else max(prof.stride(0), n)
+    _hip.check(lib.pu_h_test(_hip.ptr(prof), rows, n, ld, nmax, _hip.ptr(h), _hip.ptr(m), _hip.ptr(zs),
+                             zs.stride(0) if zs is not None else 0, _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
+               "pu_h_test")
+    return h, m, zs
+
+
+def _profiles(profiles):
+    """(float64 2-D device tensor, the input was 1-D, the input was numpy)."""
+    t = _hip.require_gpu()
+    as_numpy = not isinstance(profiles, t.Tensor)
+    x = _hip.to_device(profiles, allowed=(_hip.PU_F64,))
+    one_d = x.dim() == 1
+    if one_d:
+        x = x.reshape(1, -1)
+    if x.dim() != 2:
+        raise ValueError("profiles must be 1-D or (rows, n)")
+    return x, one_d, as_numpy
+
+
+def z_n_all(profiles, nmax=20):
+    """``Z^2_1 .. Z^2_nmax`` of each profile: float64 ``(rows, nmax)`` (a 1-D input is one
+    row).  ``2 <= n <= 8192`` bins and ``1 <= nmax <= n - 1`` (``ValueError`` otherwise)."""
+    x, _, as_numpy = _profiles(profiles)
+    _, _, zs = _h_test_device(x, nmax, True)
+    return zs.cpu().numpy() if as_numpy else zs
+
+
+def h_test(profiles, nmax=20):
+    """``(H, M)`` of each profile: scalars for a 1-D input, arrays (float64, int32) for a 2-D
+    one."""
+    x, one_d, as_numpy = _profiles(profiles)
+    h, m, _ = _h_test_device(x, nmax, False)
+    if as_numpy:
+        h, m = h.cpu().numpy(), m.cpu().numpy()
+        if one_d:
+            return float(h[0]), int(m[0])
+        return h, m
+    return (h[0], m[0]) if one_d else (h, m)
+
+
+def h_curve(plane, nmax=None):
+    """The H-versus-DM panel of the reference's ``plot_diagnostics`` (clean.py:252-253) as
+    arrays: ``h_test(row, nmax = n // 10)`` of every row of ``clean.digitize(plane)``
+    (``plane``: the dedispersed plane of ``clean.dedispersion_search``, (ndm, n)).  The
+    reference plots ``-H``; this returns ``(H, M)``.  ``digitize`` runs on the host (a folded
+    plane is small); the statistics run on the GPU."""
+    from .clean import digitize
+    plane = np.asarray(plane)
+    if plane.ndim != 2:
+        raise ValueError("h_curve: a (ndm, n) plane")
+    n = plane.shape[1]
+    if nmax is None:
+        nmax = n // 10
+    if n // 10 < 1 or int(nmax) < 1:
+        raise ValueError(f"h_curve: {n} bins give nmax = n // 10 < 1")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dig = digitize(plane.astype(np.float64))
+    return h_test(dig.astype(np.float64), nmax=int(nmax))
+
+
+def profile_stats(info, dm=None):
+    """Fill ``info``'s profile fields from ``info.allprofs`` and return ``info``.
+
+    ``disp_profile``: the sum over channels in channel order; ``dedisp_profile``:
+    ``dedispersion.dedisperse(allprofs, shifts)`` at ``dm`` (default ``info.dm``) with
+    ``sample_time = 1 / pulse_freq / nbin``.  ``disp_z2 / z6 / z12 / z20`` and ``dedisp_*``:
+    ``Z^2_m`` of the digitized profiles (``clean.digitize``), each requested at ``nmax = m``;
+    ``*_H, *_M``: :func:`h_test` at ``nmax = 20``."""
+    from .clean import digitize
+    from .dedispersion import dedisperse, dedispersion_shifts
+    if dm is None:
+        dm = info.dm
+    if dm is None:
+        raise ValueError("profile_stats: no dm given and info.dm is None")
+    allprofs = np.asarray(info.allprofs)
+    nchan, nbin = allprofs.shape
+    sample_time = 1 / info.pulse_freq / nbin
+    info.dm = float(dm)
+    info.disp_profile = np.add.reduce(allprofs.astype(np.float64), axis=0)
+    shifts = dedispersion_shifts(nchan, dm, info.start_freq, info.bandwidth, sample_time)
+    info.dedisp_profile = dedisperse(allprofs, shifts)
+    for name, prof in (("disp", info.disp_profile), ("dedisp", info.dedisp_profile)):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dig = np.asarray(digitize(np.array(prof, dtype=np.float64)), dtype=np.float64)
+        for m in (2, 6, 12, 20):
+            setattr(info, f"{name}_z{m}", float(z_n_all(dig, nmax=m)[0, -1]))
+        h, mm = h_test(dig, nmax=20)
+        setattr(info, f"{name}_H", h)
+        setattr(info, f"{name}_M", mm)
+    return info
+
+
+__all__ = ["fold_bins", "fold", "fold_file", "z_n_all", "h_test", "h_curve", "profile_stats"]
