@@ -533,6 +533,60 @@ int pu_h_test(const double *profiles, int64_t rows, int64_t n, int64_t ld, int64
               int32_t *m, double *zs, int64_t ld_zs, void *workspace, size_t workspace_bytes,
               void *stream);
 
+/* Fold series at many trial frequencies: the pulse-frequency search (no reference counterpart:
+ * the reference's PulseInfo takes pulse_freq as given).  x: device, rows series of n samples,
+ * leading dimension ld (PU_F32 / PU_F64; PU_U8 is PU_EUNSUPPORTED: a dedispersed series is never
+ * 8-bit).  phase0, dphase: device [ntrials] float64; phase0 == NULL means 0 for every trial.  For
+ * trial k sample t falls in bin b(t) by pu_fold's rule, every step one IEEE float64 operation
+ * and no fused multiply-add:
+ *     p = phase0[k] + (double)(first_sample + t) * dphase[k]
+ *     f = p - floor(p)
+ *     b = min((int64)(f * (double)nbin), nbin - 1)
+ * so host and device agree on every bin, edges included; a negative dphase, dphase = 0 and
+ * |dphase| > 1 are all legal.  The call ACCUMULATES, as pu_fold does: sums[r * ld_row + k *
+ * ld_trial + b] += the sum of (double)x[r][t] over the t with b(t) = b, counts[k * nbin + b] +=
+ * their number (counts is shared by all rows; the caller zeroes both before the first chunk;
+ * first_sample places a chunk, so the folds of the chunks of a long series add up).
+ * Arithmetic: no floating-point atomics; the order of every sum is fixed by (n, first_sample,
+ * phase0[k], dphase[k], nbin) alone: segments of 16384 samples from the chunk's start; inside
+ * a segment, maximal runs of consecutive samples of one bin (cut at the segment's end), each
+ * summed left to right; a bin's segment partial is 0.0 + its runs in time order; the partials
+ * are added in segment order from segment 0's, then to sums.  Trial k's output bits depend
+ * neither on ntrials, on k's position in the list, on rows nor on the device, and two equal
+ * calls give equal bits.  Exact whenever the values and partial sums are integers below 2^53;
+ * otherwise each call's addend to a bin is within m 2^-53 sum|x| of the exact sum of the bin's m
+ * samples.  A non-finite phase0[k] or dphase[k], or |p| >= 2^52 at either end of the chunk,
+ * cannot be rejected on the host without a synchronisation: such a trial gets NaN in all its
+ * sums (every row) and leaves its counts unchanged; the other trials are not affected.
+ * PU_EINVAL: nbin < 2; n < 0, rows < 0 or ntrials < 0; ld < n, ld_trial < nbin or ld_row <
+ * ntrials * ld_trial; a workspace smaller than pu_fold_trials_workspace_bytes(rows, n, ntrials,
+ * nbin) (rows x ceil(n / 16384) x ntrials x nbin x 8 bytes) or not 8-byte aligned.
+ * PU_EUNSUPPORTED: nbin > 256 (a trial is a lane and its bins are LDS accumulators: 64 x nbin x
+ * 8 bytes per wave within a budget of 144 KiB, next to 16 KiB of staged samples).  PU_OK without
+ * a launch for n == 0, rows == 0 or ntrials == 0.  All checked before any HIP call; asynchronous
+ * on stream. */
+size_t pu_fold_trials_workspace_bytes(int64_t rows, int64_t n, int64_t ntrials, int64_t nbin);
+int pu_fold_trials(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t first_sample,
+                   const double *phase0, const double *dphase, int64_t ntrials, int64_t nbin,
+                   double *sums, int64_t ld_trial, int64_t ld_row, int64_t *counts,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
+/* The epoch-folding statistic of folded profiles of Gaussian-noise data (Leahy et al. 1983), on
+ * pu_fold_trials' outputs.  With c_b = counts[k * nbin + b] and s_b = sums[r * ld_row + k *
+ * ld_trial + b], for row r and trial k:
+ *     chi2[r * ntrials + k] = sum over the b with c_b > 0 of (s_b - c_b mean[r])^2 / (c_b var[r])
+ * accumulated sequentially over b in float64, one IEEE operation per step as written (no fused
+ * multiply-add), and dof[k] = (the number of bins with c_b > 0) - 1.  mean, var: device [rows];
+ * chi2: device [rows * ntrials]; dof: device [ntrials] int32.  var[r] not > 0 or a non-finite
+ * s_b in any bin, empty ones included, gives NaN (so a trial pu_fold_trials filled with NaN
+ * scores NaN, not 0).  (The H-test above is Poisson-normalised, P = sum p: not the statistic of
+ * zero-mean noise.)  PU_EINVAL: nbin < 2, rows < 0 or ntrials < 0, ld_trial < nbin or ld_row <
+ * ntrials * ld_trial; PU_OK without a launch for rows == 0 or ntrials == 0.  All checked before
+ * any HIP call; asynchronous on stream. */
+int pu_profile_chi2(const double *sums, int64_t ld_trial, int64_t ld_row, const int64_t *counts,
+                    int64_t rows, int64_t ntrials, int64_t nbin, const double *mean, const double *var,
+                    double *chi2, int32_t *dof, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,10 @@ SIGNATURES = {
     "pu_fold": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _f64, _f64, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "pu_h_test_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pu_h_test": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "pu_fold_trials_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "pu_fold_trials": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _sz,
+                              _vp]),
+    "pu_profile_chi2": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pu_stream_create_cu_masked": (_i32, [_i32, ctypes.POINTER(_vp)]),
     "pu_stream_destroy": (_i32, [_vp]),
 }

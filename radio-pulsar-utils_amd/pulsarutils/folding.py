@@ -309,4 +309,184 @@ def profile_stats(info, dm=None):
     return info
 
 
-__all__ = ["fold_bins", "fold", "fold_file", "z_n_all", "h_test", "h_curve", "profile_stats"]
+# ------------------------------------------------------------------ the pulse-frequency search
+
+def frequency_grid(fmin, fmax, tobs, oversample=8):
+    """Trial frequencies ``fmin + k df``, ``df = 1 / (oversample tobs)``, for ``k = 0 ..
+    ceil((fmax - fmin) / df)``: ``oversample`` trials per independent frequency ``1 / tobs`` of
+    an observation of ``tobs`` seconds; the last one is at or just beyond ``fmax``.  Pure numpy."""
+    fmin, fmax, tobs, oversample = float(fmin), float(fmax), float(tobs), float(oversample)
+    if not fmax >= fmin:
+        raise ValueError("frequency_grid: fmax < fmin")
+    if not tobs > 0 or not oversample > 0:
+        raise ValueError("frequency_grid: tobs and oversample must be positive")
+    df = 1.0 / (oversample * tobs)
+    nk = int(np.ceil((fmax - fmin) / df))
+    return fmin + np.arange(nk + 1, dtype=np.float64) * df
+
+
+_TRIALS_WS_BYTES = 1 << 30  # pu_fold_trials' partials per call: longer trial lists go in batches
+
+
+def _series(series, what):
+    """(float32 / float64 2-D device tensor, the input was 1-D, the input was numpy)."""
+    t = _hip.require_gpu()
+    as_numpy = not isinstance(series, t.Tensor)
+    x = _hip.to_device(series, allowed=(_hip.PU_F32, _hip.PU_F64))
+    one_d = x.dim() == 1
+    if one_d:
+        x = x.reshape(1, -1)
+    if x.dim() != 2:
+        raise ValueError(f"{what}: series must be (rows, nsamples) or 1-D")
+    return x, one_d, as_numpy
+
+
+def _fold_trials_device(x, dphase, phase0, nbin, first_sample, sums, counts):
+    """pu_fold_trials of a 2-D row-major device tensor into device ``sums`` (rows, F, nbin) /
+    ``counts`` (F, nbin); ``dphase``, ``phase0``: float64 device tensors (F,).  The trial list
+    goes in batches whose partials stay under ``_TRIALS_WS_BYTES`` (a trial's bits do not
+    depend on the batch it is in)."""
+    t = _hip.torch()
+    lib = _hip.lib()
+    rows, n = x.shape
+    ntrials = dphase.numel()
+    if rows == 0 or n == 0 or ntrials == 0:
+        return
+    ld = x.stride(0) if rows > 1 else max(x.stride(0), n)
+    per_trial = max(1, lib.pu_fold_trials_workspace_bytes(rows, n, 1, nbin))
+    batch = max(1, min(ntrials, _TRIALS_WS_BYTES // per_trial))
+    ws = t.empty(max(16, lib.pu_fold_trials_workspace_bytes(rows, n, batch, nbin)), dtype=t.uint8, device=x.device)
+    for k0 in range(0, ntrials, batch):
+        nk = min(batch, ntrials - k0)
+        _hip.check(lib.pu_fold_trials(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, ld, int(first_sample),
+                                      _hip.ptr(phase0[k0:]), _hip.ptr(dphase[k0:]), nk, int(nbin),
+                                      _hip.ptr(sums[:, k0:]), sums.stride(1), sums.stride(0), _hip.ptr(counts[k0:]),
+                                      _hip.ptr(ws), ws.numel(), _hip.stream_ptr()), "pu_fold_trials")
+
+
+def _trial_phases(freqs, sample_time, ph0, device):
+    """``dphase[k] = float(sample_time) * float(freqs[k])`` (one float64 product) and ``ph0``
+    broadcast to the trials, as float64 device tensors, and the frequencies as a numpy array."""
+    t = _hip.torch()
+    if isinstance(freqs, t.Tensor):
+        freqs = freqs.detach().cpu().numpy()
+    f = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    if f.ndim != 1:
+        raise ValueError("freqs must be a scalar or 1-D")
+    if isinstance(ph0, t.Tensor):
+        ph0 = ph0.detach().cpu().numpy()
+    p = np.array(np.broadcast_to(np.asarray(ph0, dtype=np.float64), f.shape))  # (a writable copy for torch)
+    dphase = float(sample_time) * f
+    return t.from_numpy(np.ascontiguousarray(dphase)).to(device), t.from_numpy(np.ascontiguousarray(p)).to(device), f
+
+
+def fold_trials(series, freqs, sample_time, nbin, ph0=0.0, first_sample=0, out=None):
+    """Fold ``series`` (rows, nsamples; a 1-D array is one row) at every trial frequency of
+    ``freqs`` (Hz): the bin rule is :func:`fold_bins`' for each trial (``ph0``: a scalar or one
+    value per trial).
+
+    Returns ``(sums, counts)``: float64 ``(rows, F, nbin)`` (``(F, nbin)`` for a 1-D series) and
+    int64 ``(F, nbin)``, the same for every row.  ``first_sample`` places the chunk in the
+    series the phase counts from; ``out=(sums, counts)``: existing device tensors (float64
+    ``(rows, F, nbin)``, int64 ``(F, nbin)``, both contiguous) to accumulate into; they are
+    returned.  float32 and float64 series are folded as they are, other types as float64.
+    ``2 <= nbin <= 256``.  A trial whose phase is not finite or reaches 2^52 in the chunk gets
+    NaN sums and no counts.  Exact for integer-valued input below 2^53; reproducible bit for bit
+    otherwise, and a trial's result does not depend on the other trials of the call."""
+    t = _hip.require_gpu()
+    x, one_d, as_numpy = _series(series, "fold_trials")
+    nbin = int(nbin)
+    if nbin < 2:
+        raise ValueError("fold_trials: nbin must be >= 2")
+    dphase, phase0, _ = _trial_phases(freqs, sample_time, ph0, x.device)
+    rows, nf = x.shape[0], dphase.numel()
+    if out is None:
+        sums = t.zeros((rows, nf, nbin), dtype=t.float64, device=x.device)
+        counts = t.zeros((nf, nbin), dtype=t.int64, device=x.device)
+    else:
+        sums, counts = out
+        ok = (isinstance(sums, t.Tensor) and isinstance(counts, t.Tensor) and sums.dtype == t.float64
+              and counts.dtype == t.int64 and tuple(sums.shape) == (rows, nf, nbin)
+              and tuple(counts.shape) == (nf, nbin) and sums.is_contiguous() and counts.is_contiguous()
+              and sums.device == x.device and counts.device == x.device)
+        if not ok:
+            raise ValueError(f"fold_trials: out must be contiguous float64 ({rows}, {nf}, {nbin}) and int64 "
+                             f"({nf}, {nbin}) tensors on {x.device}")
+    _fold_trials_device(x, dphase, phase0, nbin, first_sample, sums, counts)
+    if out is not None:
+        return sums, counts
+    if one_d:
+        sums = sums[0]
+    if as_numpy:
+        return sums.cpu().numpy(), counts.cpu().numpy()
+    return sums, counts
+
+
+def _profile_chi2_device(sums, counts, mean, var):
+    """pu_profile_chi2 of contiguous device ``sums`` (rows, F, nbin) / ``counts`` (F, nbin) ->
+    (chi2 (rows, F) float64, dof (F,) int32) tensors."""
+    t = _hip.torch()
+    rows, nf, nbin = sums.shape
+    chi2 = t.empty((rows, nf), dtype=t.float64, device=sums.device)
+    dof = t.empty(nf, dtype=t.int32, device=sums.device)
+    _hip.check(_hip.lib().pu_profile_chi2(_hip.ptr(sums), sums.stride(1), sums.stride(0), _hip.ptr(counts), rows, nf,
+                                          nbin, _hip.ptr(mean), _hip.ptr(var), _hip.ptr(chi2), _hip.ptr(dof),
+                                          _hip.stream_ptr()), "pu_profile_chi2")
+    return chi2, dof
+
+
+def frequency_search(series, sample_time, freqs=None, fmin=None, fmax=None, nbin=32, oversample=8, chunksize=None):
+    """Epoch-folding search for a pulse frequency: fold ``series`` at every trial frequency and
+    score each profile with the chi^2 against a constant (Leahy et al. 1983; ``pu_profile_chi2``).
+
+    ``series``: one dedispersed series (1-D) or a plane of them (ndm, n), e.g. the plane of
+    ``dedispersion_search(show=True)``.  ``freqs``: the trials in Hz, or ``fmin`` and ``fmax``
+    for ``frequency_grid(fmin, fmax, n * sample_time, oversample)``.  Each row's mean and
+    variance are the population ones, ``var = E[x^2] - E[x]^2`` from float64 row sums, as
+    ``get_spectral_stats`` computes them.  ``chunksize``: fold the series that many samples at
+    a time (the partial sums of a call grow with its length).
+
+    Returns a table with one row per frequency: ``freq``, ``chi2``, ``dof`` for a 1-D series;
+    for a plane ``chi2`` is (F, ndm) and ``best_row``, ``best_chi2`` give the row with the
+    largest chi^2 at each frequency (a NaN chi^2 never wins).  The peak is
+    ``table['freq'][np.nanargmax(table['chi2'])]`` (``best_chi2`` for a plane)."""
+    from .stats import _chunk_row_sums
+    from .table import make_table
+    t = _hip.require_gpu()
+    x, one_d, _ = _series(series, "frequency_search")
+    rows, n = x.shape
+    nbin = int(nbin)
+    if nbin < 2:
+        raise ValueError("frequency_search: nbin must be >= 2")
+    if n < 1:
+        raise ValueError("frequency_search: an empty series")
+    if freqs is None:
+        if fmin is None or fmax is None:
+            raise ValueError("frequency_search: give freqs, or fmin and fmax")
+        freqs = frequency_grid(fmin, fmax, n * float(sample_time), oversample)
+    if chunksize is None:
+        chunksize = n
+    chunksize = int(chunksize)
+    if chunksize < 1:
+        raise ValueError("frequency_search: chunksize must be positive")
+    dphase, phase0, freq = _trial_phases(freqs, sample_time, 0.0, x.device)
+    nf = dphase.numel()
+    sums = t.zeros((rows, nf, nbin), dtype=t.float64, device=x.device)
+    counts = t.zeros((nf, nbin), dtype=t.int64, device=x.device)
+    for i in range(0, n, chunksize):
+        _fold_trials_device(x[:, i:i + chunksize], dphase, phase0, nbin, i, sums, counts)
+    mean = _chunk_row_sums(x, 3) / float(n)
+    var = _chunk_row_sums(x, 4) / float(n) - mean * mean
+    chi2, dof = _profile_chi2_device(sums, counts, mean, var)
+    chi2, dof = chi2.cpu().numpy(), dof.cpu().numpy()
+    if one_d:
+        return make_table({"freq": freq, "chi2": chi2[0], "dof": dof})
+    by_freq = np.ascontiguousarray(chi2.T)
+    filled = np.where(np.isnan(by_freq), -np.inf, by_freq)
+    best = np.argmax(filled, axis=1) if rows else np.zeros(nf, np.int64)
+    return make_table({"freq": freq, "chi2": by_freq, "dof": dof, "best_row": best,
+                       "best_chi2": by_freq[np.arange(nf), best] if rows else np.full(nf, np.nan)})
+
+
+__all__ = ["fold_bins", "fold", "fold_file", "z_n_all", "h_test", "h_curve", "profile_stats", "frequency_grid",
+           "fold_trials", "frequency_search"]
