@@ -130,7 +130,7 @@ def uniform_filter1d_running(lc, size=16):
     """scipy.ndimage.uniform_filter1d(lc, size) (mode 'reflect', origin 0) restated as
     scipy's running sum (ni_filters.c NI_UniformFilter1D): the first window summed from
     0.0 and divided by size, then tmp += (x[i + size - 1 - size//2] - x[i - 1 - size//2])
-    / size over the reflected line.  The order csrc/clean.hip outlier_exact_kernel
+    / size over the reflected line.  The order csrc/clean_lc.hip outlier_exact_kernel
     follows."""
     lc = np.asarray(lc, dtype=np.float64)
     n = lc.size

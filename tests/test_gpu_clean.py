@@ -236,6 +236,52 @@ def test_cut_outliers_exact_path_on_device(gpu):
     assert int(ws[0:4].view(torch.int32).item()) == 1
 
 
+def test_cut_outliers_launch_by_launch_certified(gpu):
+    """The launch-by-launch certified path of pu_cut_outliers (outlier_window_kernel,
+    outlier_std_kernel, outlier_mask_kernel), which runs when the one-launch grid would
+    not be resident.  The one-launch form takes ceil(n / 1024) segments over at most
+    CUs / 2 workgroups and at most 8 segments each, i.e. n <= (CUs / 2) * 8192: at
+    n = 1_200_000 (1172 segments) that needs 147 workgroups, so at least 294 CUs, and
+    the MI355X has 256.  The mask equals the reference's thresholding, the plane is
+    zeroed exactly on the masked columns, ws[4:8] counts them, and ws[0:4] == 0: the
+    certified kernels decided, not the exact fallback.
+
+    The seed was chosen on the CPU so that no decision can be ambiguous: with
+    L = max |lc|, no window mean lies within (2n + 64) 2^-53 L + 5e-12 sd +
+    1e-15 (L + 5 sd) (8.0e-11 here) of 5 sd or -3 sd; the nearest is 3.5e-7 away,
+    which also clears the kernels' own, wider margins (4.8e-10).  The test checks that
+    in numpy before it calls the device."""
+    import torch
+    from scipy.ndimage import uniform_filter1d
+    from pulsarutils import _hip
+    lib = _hip.lib()
+    n, nrows = 1_200_000, 2
+    rng = np.random.default_rng(42)
+    lc = rng.standard_normal(n) * 0.01
+    lc[rng.integers(0, n, 5)] += 0.3  # spikes
+    lc[rng.integers(0, n)] -= 0.3     # one dip
+    reb = uniform_filter1d(lc, 16)
+    sd = np.std(reb[::16])
+    want = (reb > 5 * sd) | (reb < -3 * sd)
+    L = np.abs(lc).max()
+    E = (2 * n + 64) * 2.0 ** -53 * L
+    gap = min(np.abs(reb - 5 * sd).min(), np.abs(reb + 3 * sd).min())
+    assert gap > E + 5e-12 * sd + 1e-15 * (L + 5 * sd)
+    assert gap > 6 * E + 5e-12 * sd + 1e-15 * (L + 5 * sd)  # the kernels' margin_up >= margin_down
+    assert (reb > 5 * sd).any() and (reb < -3 * sd).any()
+    out = torch.ones((nrows, n), dtype=torch.float64, device="cuda")
+    col = torch.from_numpy(lc).cuda()
+    ws = torch.empty(lib.pu_cut_outliers_workspace_bytes(n), dtype=torch.uint8, device="cuda")
+    mask = torch.empty(n, dtype=torch.uint8, device="cuda")
+    _hip.check(lib.pu_cut_outliers(_hip.ptr(col), n, _hip.ptr(out), nrows, out.stride(0), _hip.ptr(mask),
+                                   _hip.ptr(ws), ws.numel(), _hip.stream_ptr()), "pu_cut_outliers")
+    np.testing.assert_array_equal(mask.cpu().numpy().astype(bool), want)
+    o = out.cpu().numpy()
+    assert not o[:, want].any() and (o[:, ~want] == 1.0).all()
+    assert int(ws[4:8].view(torch.int32).item()) == int(want.sum())
+    assert int(ws[0:4].view(torch.int32).item()) == 0
+
+
 def test_zero_dm_small_cases(gpu):
     """Ragged sizes, all channels bad, no channel bad."""
     rng = np.random.default_rng(13)
