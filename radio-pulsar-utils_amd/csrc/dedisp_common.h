@@ -1,8 +1,9 @@
-// Device helpers shared by the dedispersion translation units (dedisperse.hip: the
-// float32-accumulation and channel-mode kernels and the C-ABI; dedisp_f64.hip: the float64
-// prefetching kernel, compiled with its own code-generation options).  Everything here is
-// in an anonymous namespace: each translation unit gets its own copy of these inline
-// functions and templates.  The geometry constants the host planner shares (kWaves, kD,
+// Device helpers that two or more of the dedispersion kernel units use (dedisperse.hip: the
+// subband kernel; dedisp_chan.hip: the channel-order kernel with float32 rows;
+// dedisp_f64.hip: the float64 prefetching kernel), and DedispArgs, which dedisp_host.hip
+// fills.  A helper with one user lives in that user's unit.  Everything here is in an
+// anonymous namespace: each translation unit gets its own copy of these inline functions
+// and templates.  The geometry constants the host planner shares (kWaves, kD,
 // kTPT, ...) are in dedisp_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -41,33 +42,22 @@ __device__ __forceinline__ T ld_uniform(const T *p)
     return *(const __attribute__((address_space(4))) T *)(p);
 }
 
-#ifdef PU_STAMPS
-// Diagnostic build only: a shader-clock stamp with the LDS queue drained, fenced
-// against scheduling (cdna_hip_programming.md §7, In-kernel stamps).  s_memtime is a
-// scalar-cache READ of the clock; the totals leave the kernel through vector atomics.
-__device__ __forceinline__ uint64_t stamp()
-{
-    uint64_t t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#endif
-
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// Channel-mode window reads: J x ds_read_b64 at 512-byte strides (inline asm: hipcc
+// Window reads: J x ds_read_b64 at 512-byte strides (inline asm: hipcc
 // would merge pairs into ds_read2st64_b64, which runs at half the LDS rate).  Outputs are
 // early-clobber: an LDS read can return (and write its destination) before the block's
 // later reads have consumed the address VGPR.  prefetch_window issues without a wait; the
 // registers are consumed only after wait_window() on them (a counted-free lgkmcnt(0)
 // that "defines" them, so no use can be hoisted above it).
-template <int J>
-__device__ __forceinline__ void prefetch_window(double (&w)[4], uint32_t addr)
+template <int J, int M>
+__device__ __forceinline__ void prefetch_window(double (&w)[M], uint32_t addr)
 {
+    static_assert(J <= M && (J == 2 || J == 4), "window reads");
     if constexpr (J == 4)
         asm volatile(
             "ds_read_b64 %0, %4\n\t"
@@ -115,45 +105,6 @@ __device__ __forceinline__ void pin_accumulators(Ta (&acc)[K])
         asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
     else
         asm volatile("" : "+v"(acc[0]), "+v"(acc[1]));
-}
-
-template <typename Tl>
-__device__ __forceinline__ Tl window_elem(const double (&w)[4], int k)
-{
-    if constexpr (sizeof(Tl) == 8) {
-        return w[k];
-    } else {
-        const uint64_t b = __builtin_bit_cast(uint64_t, w[k >> 1]);
-        return __builtin_bit_cast(float, (uint32_t)((k & 1) ? (b >> 32) : b));
-    }
-}
-
-// Add one channel's contribution to all D trials of this wave.  ``rec`` = 8 u16 window
-// records (byte offset | reload flag << 15); ``w`` holds trial 0's window (raw LDS
-// elements).  The window's K samples are taken into the accumulation type once per
-// window (``wv``: a float32 -> float64 conversion per changed window, not per trial and
-// sample: round 3 converted on every add, two VALU ops per float64 add at C2 acc='f64');
-// a trial whose window differs from the previous trial's re-reads it in place.
-template <typename Tl, typename Ta, int K, int J>
-__device__ __forceinline__ void channel_trials(Ta (&acc)[kD][K], double (&w)[4], const u32x4 rec, uint32_t cbase)
-{
-    Ta wv[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) wv[k] = static_cast<Ta>(window_elem<Tl>(w, k));
-#pragma unroll
-    for (int d = 0; d < kD; ++d) {
-        if (d > 0) {
-            const uint32_t word = rec[d >> 1] >> (16 * (d & 1));
-            if (word & 0x8000u) {
-                read_window<J>(w, cbase + (word & 0x7fffu));
-#pragma unroll
-                for (int k = 0; k < K; ++k) wv[k] = static_cast<Ta>(window_elem<Tl>(w, k));
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc[d][k] += wv[k];
-        pin_accumulators(acc[d]);
-    }
 }
 
 // ---- DPP cross-lane helpers (gfx9 DPP: quad_perm / row_shl / row_ror / row_bcast).
@@ -258,210 +209,6 @@ __device__ __forceinline__ T wave_max_to63(T v)
     v = max_nn(v, dpp<0x142, 0xA>(lo, v));
     v = max_nn(v, dpp<0x143, 0xC>(lo, v));
     return v;
-}
-
-// max(v, v of the DPP source lane) in one v_max_f32_dpp (rows outside ROW_MASK keep v).
-// IEEE-mode v_max_f32 returns the non-NaN operand, as fmax does; hipcc's fmax would
-// add canonicalising maxes and could not fold the DPP move.
-#define PU_MAX_DPP(NAME, CTRL)                                                                  \
-    __device__ __forceinline__ float NAME(float v)                                              \
-    {                                                                                           \
-        float r = v;                                                                            \
-        asm volatile("v_max_f32_dpp %0, %1, %0 " CTRL " bank_mask:0xf" : "+v"(r) : "v"(v));     \
-        return r;                                                                               \
-    }
-PU_MAX_DPP(max_qp1032, "quad_perm:[1,0,3,2] row_mask:0xf")
-PU_MAX_DPP(max_qp2301, "quad_perm:[2,3,0,1] row_mask:0xf")
-PU_MAX_DPP(max_ror4, "row_ror:4 row_mask:0xf")
-PU_MAX_DPP(max_ror8, "row_ror:8 row_mask:0xf")
-#undef PU_MAX_DPP
-
-__device__ __forceinline__ float vmax(float a, float b)
-{
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));  // pure: may be computed unconditionally
-    return r;
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// v_max3_f32 (IEEE mode: a NaN operand is skipped, as by v_max_f32)
-__device__ __forceinline__ float vmax3(float a, float b, float c)
-{
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// Cross-lane combines by the gfx950 permlane swaps (VALU, no LDS): one instruction
-// exchanges half of two registers, so one swap + one op reduces TWO values by a factor
-// of two in lanes.  swap32: lanes 0-31 of the result = op(a[l], a[l + 32]), lanes 32-63
-// = op(b[l - 32], b[l]).  swap16 (rows of 16 lanes): [op(a.r0, a.r1), op(b.r0, b.r1),
-// op(a.r2, a.r3), op(b.r2, b.r3)].
-template <class Op>
-__device__ __forceinline__ float swap32_combine(float a, float b, Op op)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                    false, false);
-    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-}
-template <class Op>
-__device__ __forceinline__ float swap16_combine(float a, float b, Op op)
-{
-    const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
-                                                    false, false);
-    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-}
-
-// Row of 16 lanes: every lane gets the row's sum / max (fused DPP ops).
-__device__ __forceinline__ float row_allsum(float v)
-{
-    v += dpp_undef<0xB1>(v);
-    v += dpp_undef<0x4E>(v);
-    v += dpp_undef<0x124>(v);
-    v += dpp_undef<0x128>(v);
-    return v;
-}
-__device__ __forceinline__ float row_allmax(float v)
-{
-    v = max_qp1032(v);
-    v = max_qp2301(v);
-    v = max_ror4(v);
-    return max_ror8(v);
-}
-
-// Search-mode outputs of a wave of the subband kernel for a FULL time tile (every width's
-// windows inside the series): the statistics of write_outputs (same partial record) from
-// the packed accumulator pairs, without per-sample bounds tests.
-//  * Per lane and trial: width 1 on the pairs (v_pk_*), widths 2/4/8 on scalars (the 4-
-//    and 8-sample sums are fused v_add_f32_dpp row shifts) accumulated on every lane and
-//    kept only on lanes where they are aligned windows, by one select after the loop (a
-//    conditional v_max in inline asm became an EXEC-mask branch); squares accumulated by
-//    FMA (one rounding), maxima by v_max3_f32 / v_max_f32.
-//  * Across the wave, 8 trials at once: permlane32 swaps pair trial k with k + 4 (half
-//    the lanes each), permlane16 swaps pair those with k + 2, so each of 2 registers
-//    holds 4 trials' partials in its 4 rows; 4 DPP steps finish every row.
-//    Per 8 trials and statistic: 6 swaps, 6 ops and 8 DPP steps instead of 6 DPP steps
-//    per trial (the previous epilogue: ~10 % of the kernel's wave cycles at C2).
-//  * Sums in float32 throughout: <= 14 float32 roundings per term (the shifted value, the
-//    4-term lane chain, the pair, 2 swaps, 4 row steps, the square), within the gamma =
-//    2^-20 the finalize kernel's certification assumes.
-//  * Stores: lane 16 r + i writes field i (< 13) of the record of row r's trial - one
-//    store instruction per 4 trials' records instead of one per field and trial.
-template <int D, int J>
-__device__ __forceinline__ void stats_full_pairs(const f32x2 (&acc)[D][J], const DedispArgs &a, int first, int slot0,
-                                                 int cnt, int tt, int lane)
-{
-    static_assert(D % 8 == 0, "trials per wave");
-    constexpr int NV = 9;  // per trial: sum y, sum of squares w = 1,2,4,8, max w = 1,2,4,8
-    const bool even = (lane & 1) == 0;
-    // The shift (recorded as the partial's center): the tile mean of the wave's first
-    // trial.  The wave's D trials are a few DM steps apart, so their tile means differ by
-    // a small fraction of the std: the shifted squares stay near the variance and their
-    // float32 sums stay accurate, which keeps the finalize's certification bound tight
-    // (lane 0's first sample as the shift inflated them by w^2 var).
-    float kt;
-    {
-        f32x2 s0 = acc[0][0];
-#pragma unroll
-        for (int j = 1; j < J; ++j) s0 += acc[0][j];
-        const float v = wave_sum_to63(s0.x + s0.y);
-        kt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63)) *
-             (1.0f / (128.0f * J));
-    }
-    const f32x2 k1 = {kt, kt};
-    const float k2 = 2.0f * kt, k4 = 4.0f * kt, k8 = 8.0f * kt;
-    static_assert(J % 2 == 0, "sample pairs are taken two blocks at a time");
-    const bool lo2 = (lane & 2) == 0;
-    auto lane_stats = [&](int d, float (&v)[NV]) {
-        f32x2 s1 = {0.0f, 0.0f}, q1 = s1;
-        float q2 = 0.0f, q4 = 0.0f, q8 = 0.0f;
-        float m1 = -INFINITY, m2 = -INFINITY, m4 = -INFINITY, m8 = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < J; j += 2) {
-            float r2[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const f32x2 x = acc[d][j + h];
-                const f32x2 y = x - k1;
-                s1 += y;
-                q1 = __builtin_elementwise_fma(y, y, q1);
-                m1 = vmax3(m1, x.x, x.y);
-                r2[h] = x.x + x.y;  // width 2 (every lane)
-                const float y2 = r2[h] - k2;
-                q2 = __builtin_fmaf(y2, y2, q2);
-                m2 = vmax(m2, r2[h]);
-            }
-            // widths 4 and 8 of the two blocks j, j + 1 packed into one register (every
-            // lane useful, round 4): even lanes hold block j's width-4 sums (r2 of lanes l,
-            // l + 1), odd lanes block j + 1's (lanes l - 1, l) - one quad_perm [1,0,3,2] add
-            // of the parity-swapped r2; then quad_perm [2,3,0,1] pairs them into width 8 on
-            // lanes 4k (block j) and 4k + 1 (block j + 1), the other two lanes of each quad
-            // holding copies (dropped after the loop).  (Round 3: both widths on every lane
-            // of every block, half / three quarters of them dropped.)
-            const float a4 = even ? r2[0] : r2[1];
-            const float c4 = even ? r2[1] : r2[0];
-            const float r4 = a4 + dpp<0xB1>(0.0f, c4);
-            const float y4 = r4 - k4;
-            q4 = __builtin_fmaf(y4, y4, q4);
-            m4 = vmax(m4, r4);
-            const float r8 = r4 + dpp<0x4E>(0.0f, r4);
-            const float y8 = r8 - k8;
-            q8 = __builtin_fmaf(y8, y8, q8);
-            m8 = vmax(m8, r8);
-        }
-        v[0] = s1.x + s1.y;
-        v[1] = q1.x + q1.y;
-        v[2] = q2;
-        v[3] = q4;
-        v[4] = lo2 ? q8 : 0.0f;
-        v[5] = m1;
-        v[6] = m2;
-        v[7] = m4;
-        v[8] = lo2 ? m8 : -INFINITY;
-    };
-    auto add = [](float x, float y) { return x + y; };
-    auto mx = [](float x, float y) { return vmax(x, y); };
-    // record field f = lane & 15 (< 13): kt | max w, sum, sum of squares w (w = 1, 2, 4, 8)
-    const int f = lane & 15, row = lane >> 4;
-    const int fw = (f - 1) / 3, fk = (f - 1) % 3;  // f >= 1: width index, 0 max / 1 sum / 2 squares
-    // 8 trials at a time (b0 .. b0 + 7): the register footprint of the 16-trial shapes'
-    // two passes is that of one
-#pragma unroll
-    for (int b0 = 0; b0 < D; b0 += 8) {
-        // trials k and k + 4 -> U[k] (lanes 0-31: k, 32-63: k + 4)
-        float U[4][NV];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float va[NV], vb[NV];
-            lane_stats(b0 + k, va);
-            lane_stats(b0 + k + 4, vb);
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-                U[k][i] = i < 5 ? swap32_combine(va[i], vb[i], add) : swap32_combine(va[i], vb[i], mx);
-        }
-        // U[j] and U[j + 2] -> W[j]: row r holds trial j + 2 r
-        float W[2][NV];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-                W[j][i] = i < 5 ? row_allsum(swap16_combine(U[j][i], U[j + 2][i], add))
-                                : row_allmax(swap16_combine(U[j][i], U[j + 2][i], mx));
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float v = kt;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                v = (f >= 1 && fw == w && fk == 0) ? W[j][5 + w] : v;
-                v = (f >= 1 && fw == w && fk == 1) ? W[j][0] : v;
-                v = (f >= 1 && fw == w && fk == 2) ? W[j][1 + w] : v;
-            }
-            const int trial = b0 + j + 2 * row;
-            if (f < 13 && slot0 + trial < cnt)
-                reinterpret_cast<float *>(a.partials)[((size_t)(first + slot0 + trial) * a.ntt + tt) * kPartStride + f] = v;
-        }
-    }
 }
 
 // float64 counterparts of the permlane combines (two swaps per value, one per dword)
@@ -745,8 +492,6 @@ __device__ __forceinline__ void write_outputs(const Ta (&acc)[D][K], const Dedis
         }
     }
 }
-
-typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
 // LDS-DMA of one channel-row window [start, start + cover) mod n (float32) into dst:
 // 1 KiB pieces (16 B/lane) while contiguous, per-lane modular dwords if it wraps.

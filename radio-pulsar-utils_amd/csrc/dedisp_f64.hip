@@ -3,13 +3,15 @@
 // -mllvm -structurizecfg-skip-uniform-regions=true: the kernel's per-trial state machine
 // is an unstructured graph of UNIFORM branches, which the AMDGPU structurizer would
 // otherwise rewrite into flag-guarded flow blocks with register copies at every join
-// (the first draft spilled 450 bytes per lane).  dedisperse.hip keeps its own options.
+// (the first draft spilled 450 bytes per lane).  The other dedispersion units are compiled
+// with the same option by their own choice (csrc/Makefile).
 //
 // Replaces the reference hot loop of dedisperse / _dedisperse / roll_and_sum
 // (pulsarutils/dedispersion.py:60-98) with float64 accumulators: bit-identical series.
 #include <hip/hip_runtime.h>
 
 #include "dedisp_common.h"
+#include "dedisp_units.h"
 
 // the state machine's entry labels (T0_0) are reached by falling through
 #pragma clang diagnostic ignored "-Wunused-label"
@@ -45,7 +47,7 @@ namespace {
 //     SQ_INSTS_VALU at C2, profiles/r05/counters/).
 // Record per (DM tile, channel, wave): D u16 words, word d = 0 when trial d reads trial
 // d - 1's window, else 1 + the offset in float64 elements, from the chunk's row base, of
-// the window to prefetch when trial d's becomes current (planner: dedisperse.hip, pu_plan create).  A
+// the window to prefetch when trial d's becomes current (planner: plan.cpp, plan_channels).  A
 // table after the records holds each channel's first window offset (read at chunk starts).
 // Channel order and the float64 adds are the reference's (dedispersion.py:86-98): the
 // series is bit-identical.
@@ -339,7 +341,8 @@ int launch(bool plane, const DedispArgs &a, size_t lds_bytes, const int32_t *fir
 
 }  // namespace
 
-// Called by dedisperse.hip's dispatch (plain types across the translation units).
+// Called by dedisp_host.hip's dispatch (plain types across the translation units:
+// dedisp_units.h).
 int pu_dd_launch_f64(bool tin_f32, bool plane, const void *args, size_t args_bytes, size_t lds_bytes,
                      const int32_t *first, const int32_t *count, const int32_t *rowlen, const int32_t *base,
                      const void *rec8, const void *first_off, void *stream, int waves)

@@ -1,6 +1,7 @@
-// Dedispersion geometry shared by the kernels (dedisperse.hip, dedisp_f64.hip through
-// dedisp_common.h) and the host planner (plan.cpp), and the planner's interface.  Plain
-// C++17: no HIP header, no device code, so the planner's unit cannot reach the device.
+// Dedispersion geometry shared by the kernel units (dedisperse.hip, dedisp_chan.hip,
+// dedisp_f64.hip, dedisp_finalize.hip), the plan object's unit (dedisp_host.hip) and the
+// host planner (plan.cpp), and the planner's interface.  Plain C++17: no HIP header, no
+// device code, so the planner's unit cannot reach the device.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -85,7 +86,7 @@ inline int pick_variant(int dtype, int acc)
 namespace pu {
 
 // Table records the kernels read as clang vector types (u32x4, i32x4, i32x2): the same
-// layout as plain structs (dedisperse.hip asserts the sizes; the upload copies bytes).
+// layout as plain structs (dedisp_units.h asserts the sizes; the upload copies bytes).
 struct PlanU32x4 {
     uint32_t x, y, z, w;
 };

@@ -1,235 +1,13 @@
-// Incoherent (brute-force) shift-and-sum dedispersion for gfx950 (MI355X).
+// Incoherent (brute-force) shift-and-sum dedispersion for gfx950 (MI355X): the subband
+// kernel (float32 accumulation of u8 / f32 / f64 inputs) and its launch
+// code.  The channel-order kernels are dedisp_chan.hip and dedisp_f64.hip, the finalize
+// kernel dedisp_finalize.hip, the plan object and the C ABI dedisp_host.hip.
 //
 // Replaces the reference hot loop (pulsarutils/dedispersion.py):
 //   _dedispersion_search :174-202  (prange over trials -> workgroups over DM tiles)
 //   dedisperse/_dedisperse/roll_and_sum :60-98 (circular shift-and-sum, channel order)
 //
 // out_d[t] = sum_c x[c][(t + s[d][c]) mod N]   (s = dedispersion_shifts, any sign)
-//
-// Mapping:
-//   * one workgroup = 8 waves = one DM tile (64 trials) x one time tile; each wave
-//     owns D = 8 trials, lane l owns K samples (float: t0 + 2l + 128j + e, j<4, e<2)
-//     -> D*K accumulators in VGPRs.
-//   * channel rows are staged in LDS, ncc channels per chunk, each row covering
-//     [t0 + smin_c, t0 + TT + smax_c) mod N: the tile's modular halo.  Rows arrive by
-//     LDS-DMA (global_load_lds, 1 KiB pieces, per-lane modular addresses only for
-//     the rare windows that wrap) into a two-buffer ring: chunk k+1 lands while chunk
-//     k is summed.  Converting inputs (u8, f64 -> f32 LDS) use register staging.
-//   * per (tile, channel, wave) the host precomputes 8 x u16 "window records": the LDS
-//     byte offset of each trial's K-sample window (alignment copy included) and, in
-//     bit 15, whether it differs from the previous trial's.  One scalar load per
-//     channel; per trial one s_bitcmp1 + branch; the window is re-read (in place, 4 x
-//     ds_read_b64) only when it changes -- adjacent plan trials differ by <= 1 sample
-//     per channel, so most v_add_f32 reuse registers.  The first window of the next
-//     channel is prefetched into the other window buffer while this one is summed.
-//   * accumulation in channel order 0..nchan-1 (reference order: with a float64
-//     accumulator the series is bit-identical).
-//   * epilogue: the dedispersed plane, or per-tile partial statistics of the
-//     1/2/4/8-sample rebinned series reduced by pu_finalize_kernel in a fixed order.
-//   * blockIdx is remapped XCD-aware so all DM tiles of a time tile run on one XCD.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <mutex>
-#include <type_traits>
-#include <vector>
-
-#include "exact.h"
-#include "pu_common.h"
-
-#include "dedisp_common.h"
-#include "dedisp_plan.h"
-
-// The planner (plan.cpp, plain C++): its functions are found through these types.
-using pu::PlanProblem;
-using pu::PlanTables;
-
-// dedisp_f64.hip (waves: dedisp_plan.h's kF64Waves, checked against the kernel's)
-int pu_dd_launch_f64(bool tin_f32, bool plane, const void *args, size_t args_bytes, size_t lds_bytes,
-                     const int32_t *first, const int32_t *count, const int32_t *rowlen, const int32_t *base,
-                     const void *rec8, const void *first_off, void *stream, int waves);
-
-namespace {
-
-template <typename Tin, typename Tl, typename Ta, bool PLANE, bool STATS>
-// 4 waves per SIMD (2 workgroups per CU): <= 128 VGPRs, enforced (the float64 epilogue
-// left alone took 130, i.e. 3 waves per SIMD)
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4)))
-dedisp_kernel(DedispArgs a, const int32_t *__restrict__ tile_first, const int32_t *__restrict__ tile_count,
-              const int32_t *__restrict__ tile_rowlen, const int32_t *__restrict__ base_tab,
-              const u32x4 *__restrict__ rec_tab)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool kDma = std::is_same<Tin, Tl>::value;
-    constexpr int SZ = (int)sizeof(Tl);
-    constexpr int E = 8 / SZ;     // samples per 8-byte LDS read
-    // reads per window: 4, or 2 when float32 rows feed float64 accumulators (8 trials x 8
-    // float64 samples per lane would take 164 VGPRs: 3 waves per SIMD)
-    constexpr int J = (sizeof(Ta) == 8 && sizeof(Tl) == 4) ? 2 : 4;
-    constexpr int K = E * J;      // samples per lane
-    constexpr int TT = 64 * K;    // samples per time tile
-    constexpr int D = kD;
-
-    const int wg = pu::xcd_remap(blockIdx.x, gridDim.x);
-    const int dt = a.dt0 + wg % a.ndt;
-    const int tt = a.tt0 + wg / a.ndt;
-    const int t0 = tt * TT;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int first = ld_uniform(tile_first + dt);
-    const int cnt = ld_uniform(tile_count + dt);
-    const int rowlen = ld_uniform(tile_rowlen + dt);
-    const int slot0 = wave * D;
-    const bool active = slot0 < cnt;
-    const int n = a.n;
-    const int stride = a.row_stride;           // elements per row copy
-    const int copy_bytes = stride * SZ;
-    const int chan_bytes = E * copy_bytes;
-    const int buf_bytes = a.ncc * chan_bytes;
-    // LDS byte address of the dynamic region (local-address-space pointer -> 32-bit offset)
-    const uint32_t smem_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;
-
-    Ta acc[D][K];
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc[d][k] = Ta(0);
-
-    const int32_t *base = base_tab + (size_t)dt * a.nchan;
-    const u32x4 *recs = rec_tab + (size_t)dt * a.nchan * kWaves + wave;
-    const Tin *data = reinterpret_cast<const Tin *>(a.data);
-    const int nchunks = (a.nchan + a.ncc - 1) / a.ncc;
-    // bytes of a row copy actually moved (whole 256-byte pieces)
-    const int cover_bytes = (rowlen * SZ + 255) & ~255;
-    const int cover = cover_bytes / SZ;
-
-    // ---- LDS-DMA of chunk k into ring buffer b: each wave moves whole row copies
-    auto issue_dma = [&](int k, int b) {
-        const int c0 = k * a.ncc;
-        const int nc = min(a.ncc, a.nchan - c0);
-        const uint32_t bufo = (uint32_t)(b * buf_bytes);
-        for (int r = wave; r < nc * E; r += kWaves) {
-            const int ci = r / E, q = r % E;
-            const int c = c0 + ci;
-            const char *row = reinterpret_cast<const char *>(data + (size_t)c * (size_t)a.ld);
-            int start = ld_uniform(base + c) + t0 + q;
-            if (start >= n) start -= n;
-            if (start >= n) start -= n;
-            unsigned char *dst = smem + bufo + ci * chan_bytes + q * copy_bytes;
-            if (!a.small_n && start + cover <= n) {
-                // contiguous window: 1 KiB pieces (16 B/lane), then 256 B pieces
-                const char *src = row + (size_t)start * SZ;
-                int off = 0;
-                for (; off + 1024 <= cover_bytes; off += 1024)
-                    __builtin_amdgcn_global_load_lds((const void *)(src + off + 16 * lane),
-                                                     (__attribute__((address_space(3))) void *)(dst + off), 16, 0, 0);
-                for (; off < cover_bytes; off += 256)
-                    __builtin_amdgcn_global_load_lds((const void *)(src + off + 4 * lane),
-                                                     (__attribute__((address_space(3))) void *)(dst + off), 4, 0, 0);
-            } else {
-                // wrapping window: per-lane modular element index, 4 B per lane
-                for (int off = 0; off < cover_bytes; off += 256) {
-                    const int byte = off + 4 * lane;
-                    int idx = start + byte / SZ;
-                    if (!a.small_n) {
-                        idx = idx >= n ? idx - n : idx;
-                    } else {
-                        idx %= n;
-                    }
-                    const char *src = row + (size_t)idx * SZ + (byte % SZ);
-                    __builtin_amdgcn_global_load_lds((const void *)src,
-                                                     (__attribute__((address_space(3))) void *)(dst + off), 4, 0, 0);
-                }
-            }
-        }
-    };
-
-    // ---- register staging for converting inputs (u8 -> f32, f64 -> f32)
-    auto stage_regs = [&](int k) {
-        const int c0 = k * a.ncc;
-        const int nc = min(a.ncc, a.nchan - c0);
-        for (int ci = 0; ci < nc; ++ci) {
-            const int c = c0 + ci;
-            const Tin *row = data + (size_t)c * (size_t)a.ld;
-            int start = ld_uniform(base + c) + t0;
-            if (start >= n) start -= n;
-            Tl *dst = reinterpret_cast<Tl *>(smem + ci * chan_bytes);
-            const int len = rowlen + E - 1;
-            for (int j = tid; j < len; j += kThreads) {
-                int idx = start + j;
-                if (!a.small_n) {
-                    if (idx >= n) idx -= n;
-                } else {
-                    idx %= n;
-                }
-                const Tl v = static_cast<Tl>(row[idx]);
-                if (j < rowlen) dst[j] = v;
-                if constexpr (E == 2) {
-                    if (j >= 1) dst[stride + j - 1] = v;
-                }
-            }
-        }
-    };
-
-    if constexpr (kDma) issue_dma(0, 0);
-    for (int k = 0; k < nchunks; ++k) {
-        const int c0 = k * a.ncc;
-        const int nc = min(a.ncc, a.nchan - c0);
-        const int b = kDma ? (k & 1) : 0;
-        if constexpr (kDma) asm volatile("s_waitcnt vmcnt(0)" : : : "memory");  // explicit (see dedisp_sub_kernel)
-        __syncthreads();  // this wave's DMA landed and every wave left the other buffer
-        if constexpr (kDma) {
-            if (k + 1 < nchunks) issue_dma(k + 1, b ^ 1);
-        } else {
-            stage_regs(k);
-            __syncthreads();
-        }
-        if (!active) continue;
-        // ---- accumulate the chunk: channel pairs alternate window buffers so the next
-        // channel's first window is read while this one is summed.  (Round 4 tried reads
-        // one trial ahead of the adds instead, with a copy per changed window: C1 0.076
-        // vs 0.068 ms.)
-        const uint32_t rows_lane = smem_addr + (uint32_t)(b * buf_bytes) + 8u * lane;
-        double w0[4], w1[4];
-        const u32x4 *rc = recs + (size_t)c0 * kWaves;
-        u32x4 rec0 = ld_uniform(rc);
-        u32x4 rec1 = nc > 1 ? ld_uniform(rc + kWaves) : rec0;
-        read_window<J>(w0, rows_lane + (rec0[0] & 0x7fffu));
-        for (int ci = 0; ci < nc; ci += 2) {
-            const uint32_t cb0 = rows_lane + (uint32_t)(ci * chan_bytes);
-            const bool has1 = ci + 1 < nc, has2 = ci + 2 < nc, has3 = ci + 3 < nc;
-            u32x4 rec2 = rec0, rec3 = rec1;
-            if (has2) rec2 = ld_uniform(rc + (size_t)(ci + 2) * kWaves);  // two channels ahead
-            if (has1) prefetch_window<J>(w1, cb0 + chan_bytes + (rec1[0] & 0x7fffu));
-            channel_trials<Tl, Ta, K, J>(acc, w0, rec0, cb0);
-            if (!has1) break;
-            wait_window<J>(w1);
-            if (has3) rec3 = ld_uniform(rc + (size_t)(ci + 3) * kWaves);
-            if (has2) prefetch_window<J>(w0, cb0 + 2 * chan_bytes + (rec2[0] & 0x7fffu));
-            channel_trials<Tl, Ta, K, J>(acc, w1, rec1, cb0 + chan_bytes);
-            if (has2) wait_window<J>(w0);
-            rec0 = rec2;
-            rec1 = rec3;
-        }
-    }
-    if (!active) return;
-
-    if constexpr (STATS && !PLANE && sizeof(Ta) == 8) {
-        if (t0 + TT <= n) {  // full tile: the permlane epilogue
-            stats_full_f64<E, K>(acc, a, first, slot0, cnt, tt, lane);
-            return;
-        }
-    }
-    write_outputs<Tl, Ta, K, kD, PLANE, STATS>(acc, a, first, slot0, cnt, t0, tt, lane);
-}
-
-
-// ---------------------------------------------------------------------------------
-// Subband mode (float32 accumulation of u8 / f32 / f64 inputs) -- DESIGN.md §4.2.
 //
 // Channels are taken in groups of G adjacent channels.  For trial d and group g the
 // shifts are s_{d,c0+k} = b_d + v_k, with b_d the group's first-channel shift and v the
@@ -250,12 +28,235 @@ dedisp_kernel(DedispArgs a, const int32_t *__restrict__ tile_first, const int32_
 // G x fewer adds than channel mode.
 //
 // Lane l of a wave owns samples t0 + 2l + 128j + e (j < K/2, e < 2) of D trials.
-typedef int i32x2 __attribute__((ext_vector_type(2)));
+#include <hip/hip_runtime.h>
 
-// the planner fills these records as plain structs; DeviceTables::upload copies their bytes
-static_assert(sizeof(pu::PlanU32x4) == sizeof(u32x4) && sizeof(pu::PlanI32x4) == sizeof(i32x4) &&
-                  sizeof(pu::PlanI32x2) == sizeof(i32x2),
-              "plan table records");
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <type_traits>
+
+#include "pu_common.h"
+
+#include "dedisp_common.h"
+#include "dedisp_units.h"
+
+namespace {
+
+#ifdef PU_STAMPS
+// Diagnostic build only: a shader-clock stamp with the LDS queue drained, fenced
+// against scheduling (cdna_hip_programming.md §7, In-kernel stamps).  s_memtime is a
+// scalar-cache READ of the clock; the totals leave the kernel through vector atomics.
+__device__ __forceinline__ uint64_t stamp()
+{
+    uint64_t t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#endif
+
+// max(v, v of the DPP source lane) in one v_max_f32_dpp (rows outside ROW_MASK keep v).
+// IEEE-mode v_max_f32 returns the non-NaN operand, as fmax does; hipcc's fmax would
+// add canonicalising maxes and could not fold the DPP move.
+#define PU_MAX_DPP(NAME, CTRL)                                                                  \
+    __device__ __forceinline__ float NAME(float v)                                              \
+    {                                                                                           \
+        float r = v;                                                                            \
+        asm volatile("v_max_f32_dpp %0, %1, %0 " CTRL " bank_mask:0xf" : "+v"(r) : "v"(v));     \
+        return r;                                                                               \
+    }
+PU_MAX_DPP(max_qp1032, "quad_perm:[1,0,3,2] row_mask:0xf")
+PU_MAX_DPP(max_qp2301, "quad_perm:[2,3,0,1] row_mask:0xf")
+PU_MAX_DPP(max_ror4, "row_ror:4 row_mask:0xf")
+PU_MAX_DPP(max_ror8, "row_ror:8 row_mask:0xf")
+#undef PU_MAX_DPP
+
+__device__ __forceinline__ float vmax(float a, float b)
+{
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));  // pure: may be computed unconditionally
+    return r;
+}
+
+// v_max3_f32 (IEEE mode: a NaN operand is skipped, as by v_max_f32)
+__device__ __forceinline__ float vmax3(float a, float b, float c)
+{
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+// Cross-lane combines by the gfx950 permlane swaps (VALU, no LDS): one instruction
+// exchanges half of two registers, so one swap + one op reduces TWO values by a factor
+// of two in lanes.  swap32: lanes 0-31 of the result = op(a[l], a[l + 32]), lanes 32-63
+// = op(b[l - 32], b[l]).  swap16 (rows of 16 lanes): [op(a.r0, a.r1), op(b.r0, b.r1),
+// op(a.r2, a.r3), op(b.r2, b.r3)].
+template <class Op>
+__device__ __forceinline__ float swap32_combine(float a, float b, Op op)
+{
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
+                                                    false, false);
+    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+}
+template <class Op>
+__device__ __forceinline__ float swap16_combine(float a, float b, Op op)
+{
+    const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
+                                                    false, false);
+    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+}
+
+// Row of 16 lanes: every lane gets the row's sum / max (fused DPP ops).
+__device__ __forceinline__ float row_allsum(float v)
+{
+    v += dpp_undef<0xB1>(v);
+    v += dpp_undef<0x4E>(v);
+    v += dpp_undef<0x124>(v);
+    v += dpp_undef<0x128>(v);
+    return v;
+}
+__device__ __forceinline__ float row_allmax(float v)
+{
+    v = max_qp1032(v);
+    v = max_qp2301(v);
+    v = max_ror4(v);
+    return max_ror8(v);
+}
+
+// Search-mode outputs of a wave of the subband kernel for a FULL time tile (every width's
+// windows inside the series): the statistics of write_outputs (same partial record) from
+// the packed accumulator pairs, without per-sample bounds tests.
+//  * Per lane and trial: width 1 on the pairs (v_pk_*), widths 2/4/8 on scalars (the 4-
+//    and 8-sample sums are fused v_add_f32_dpp row shifts) accumulated on every lane and
+//    kept only on lanes where they are aligned windows, by one select after the loop (a
+//    conditional v_max in inline asm became an EXEC-mask branch); squares accumulated by
+//    FMA (one rounding), maxima by v_max3_f32 / v_max_f32.
+//  * Across the wave, 8 trials at once: permlane32 swaps pair trial k with k + 4 (half
+//    the lanes each), permlane16 swaps pair those with k + 2, so each of 2 registers
+//    holds 4 trials' partials in its 4 rows; 4 DPP steps finish every row.
+//    Per 8 trials and statistic: 6 swaps, 6 ops and 8 DPP steps instead of 6 DPP steps
+//    per trial (the previous epilogue: ~10 % of the kernel's wave cycles at C2).
+//  * Sums in float32 throughout: <= 14 float32 roundings per term (the shifted value, the
+//    4-term lane chain, the pair, 2 swaps, 4 row steps, the square), within the gamma =
+//    2^-20 the finalize kernel's certification assumes.
+//  * Stores: lane 16 r + i writes field i (< 13) of the record of row r's trial - one
+//    store instruction per 4 trials' records instead of one per field and trial.
+template <int D, int J>
+__device__ __forceinline__ void stats_full_pairs(const f32x2 (&acc)[D][J], const DedispArgs &a, int first, int slot0,
+                                                 int cnt, int tt, int lane)
+{
+    static_assert(D % 8 == 0, "trials per wave");
+    constexpr int NV = 9;  // per trial: sum y, sum of squares w = 1,2,4,8, max w = 1,2,4,8
+    const bool even = (lane & 1) == 0;
+    // The shift (recorded as the partial's center): the tile mean of the wave's first
+    // trial.  The wave's D trials are a few DM steps apart, so their tile means differ by
+    // a small fraction of the std: the shifted squares stay near the variance and their
+    // float32 sums stay accurate, which keeps the finalize's certification bound tight
+    // (lane 0's first sample as the shift inflated them by w^2 var).
+    float kt;
+    {
+        f32x2 s0 = acc[0][0];
+#pragma unroll
+        for (int j = 1; j < J; ++j) s0 += acc[0][j];
+        const float v = wave_sum_to63(s0.x + s0.y);
+        kt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63)) *
+             (1.0f / (128.0f * J));
+    }
+    const f32x2 k1 = {kt, kt};
+    const float k2 = 2.0f * kt, k4 = 4.0f * kt, k8 = 8.0f * kt;
+    static_assert(J % 2 == 0, "sample pairs are taken two blocks at a time");
+    const bool lo2 = (lane & 2) == 0;
+    auto lane_stats = [&](int d, float (&v)[NV]) {
+        f32x2 s1 = {0.0f, 0.0f}, q1 = s1;
+        float q2 = 0.0f, q4 = 0.0f, q8 = 0.0f;
+        float m1 = -INFINITY, m2 = -INFINITY, m4 = -INFINITY, m8 = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < J; j += 2) {
+            float r2[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const f32x2 x = acc[d][j + h];
+                const f32x2 y = x - k1;
+                s1 += y;
+                q1 = __builtin_elementwise_fma(y, y, q1);
+                m1 = vmax3(m1, x.x, x.y);
+                r2[h] = x.x + x.y;  // width 2 (every lane)
+                const float y2 = r2[h] - k2;
+                q2 = __builtin_fmaf(y2, y2, q2);
+                m2 = vmax(m2, r2[h]);
+            }
+            // widths 4 and 8 of the two blocks j, j + 1 packed into one register (every
+            // lane useful, round 4): even lanes hold block j's width-4 sums (r2 of lanes l,
+            // l + 1), odd lanes block j + 1's (lanes l - 1, l) - one quad_perm [1,0,3,2] add
+            // of the parity-swapped r2; then quad_perm [2,3,0,1] pairs them into width 8 on
+            // lanes 4k (block j) and 4k + 1 (block j + 1), the other two lanes of each quad
+            // holding copies (dropped after the loop).  (Round 3: both widths on every lane
+            // of every block, half / three quarters of them dropped.)
+            const float a4 = even ? r2[0] : r2[1];
+            const float c4 = even ? r2[1] : r2[0];
+            const float r4 = a4 + dpp<0xB1>(0.0f, c4);
+            const float y4 = r4 - k4;
+            q4 = __builtin_fmaf(y4, y4, q4);
+            m4 = vmax(m4, r4);
+            const float r8 = r4 + dpp<0x4E>(0.0f, r4);
+            const float y8 = r8 - k8;
+            q8 = __builtin_fmaf(y8, y8, q8);
+            m8 = vmax(m8, r8);
+        }
+        v[0] = s1.x + s1.y;
+        v[1] = q1.x + q1.y;
+        v[2] = q2;
+        v[3] = q4;
+        v[4] = lo2 ? q8 : 0.0f;
+        v[5] = m1;
+        v[6] = m2;
+        v[7] = m4;
+        v[8] = lo2 ? m8 : -INFINITY;
+    };
+    auto add = [](float x, float y) { return x + y; };
+    auto mx = [](float x, float y) { return vmax(x, y); };
+    // record field f = lane & 15 (< 13): kt | max w, sum, sum of squares w (w = 1, 2, 4, 8)
+    const int f = lane & 15, row = lane >> 4;
+    const int fw = (f - 1) / 3, fk = (f - 1) % 3;  // f >= 1: width index, 0 max / 1 sum / 2 squares
+    // 8 trials at a time (b0 .. b0 + 7): the register footprint of the 16-trial shapes'
+    // two passes is that of one
+#pragma unroll
+    for (int b0 = 0; b0 < D; b0 += 8) {
+        // trials k and k + 4 -> U[k] (lanes 0-31: k, 32-63: k + 4)
+        float U[4][NV];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float va[NV], vb[NV];
+            lane_stats(b0 + k, va);
+            lane_stats(b0 + k + 4, vb);
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+                U[k][i] = i < 5 ? swap32_combine(va[i], vb[i], add) : swap32_combine(va[i], vb[i], mx);
+        }
+        // U[j] and U[j + 2] -> W[j]: row r holds trial j + 2 r
+        float W[2][NV];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+                W[j][i] = i < 5 ? row_allsum(swap16_combine(U[j][i], U[j + 2][i], add))
+                                : row_allmax(swap16_combine(U[j][i], U[j + 2][i], mx));
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float v = kt;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                v = (f >= 1 && fw == w && fk == 0) ? W[j][5 + w] : v;
+                v = (f >= 1 && fw == w && fk == 1) ? W[j][0] : v;
+                v = (f >= 1 && fw == w && fk == 2) ? W[j][1 + w] : v;
+            }
+            const int trial = b0 + j + 2 * row;
+            if (f < 13 && slot0 + trial < cnt)
+                reinterpret_cast<float *>(a.partials)[((size_t)(first + slot0 + trial) * a.ntt + tt) * kPartStride + f] = v;
+        }
+    }
+}
 
 struct SubArgs {
     DedispArgs o;           // data, ld, nchan, n, ndt, ntt, small_n; plane / partials
@@ -271,59 +272,27 @@ struct SubArgs {
     void *stamps;           // diagnostic build (PU_STAMPS): 8 x u64 phase-cycle totals
 };
 
-// Counted LDS wait that also "defines" the J window registers it guards, so the adds
-// that read them cannot be hoisted above it.  lgkmcnt counts the inline-asm reads in
-// issue order; an LDS op issued earlier or an outstanding scalar load only makes the
-// wait longer, never shorter.
-#define PU_WAIT_CASE(N)                                                                        \
-    if constexpr (J == 4)                                                                      \
-        asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) \
-                     : : "memory");                                                            \
-    else                                                                                       \
-        asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(w[0]), "+v"(w[1]) : : "memory");
+// Counted LDS wait, s_waitcnt lgkmcnt(N), that also "defines" the register it guards, so
+// the instructions that read it cannot be hoisted above it.  lgkmcnt counts the inline-asm
+// reads in issue order; an LDS op issued earlier or an outstanding scalar load only makes
+// the wait longer, never shorter.
+template <int N, typename T>
+__device__ __forceinline__ void wait_lgkm(T &v)
+{
+    static_assert(N >= 0 && N <= 15, "lgkmcnt");
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
+}
 
-template <int J, int N>
-__device__ __forceinline__ void wait_window_n(double (&w)[J])
+// the same for the J registers of a window
+template <int N, int J>
+__device__ __forceinline__ void wait_lgkm(double (&w)[J])
 {
     static_assert(J == 2 || J == 4, "window reads");
-    static_assert(N % J == 0 && N <= 3 * J, "lgkmcnt");
-    if constexpr (N == 12) {
-        PU_WAIT_CASE(12)
-    } else if constexpr (N == 8) {
-        PU_WAIT_CASE(8)
-    } else if constexpr (N == 6) {
-        PU_WAIT_CASE(6)
-    } else if constexpr (N == 4) {
-        PU_WAIT_CASE(4)
-    } else if constexpr (N == 2) {
-        PU_WAIT_CASE(2)
-    } else {
-        PU_WAIT_CASE(0)
-    }
-}
-#undef PU_WAIT_CASE
-
-// J x ds_read_b64 of one window (no wait).  Inline asm: hipcc would merge pairs into
-// ds_read2st64_b64, which runs at half the LDS rate.
-template <int J>
-__device__ __forceinline__ void issue_window(double (&w)[J], uint32_t addr)
-{
+    static_assert(N >= 0 && N <= 15, "lgkmcnt");
     if constexpr (J == 4)
-        asm volatile(
-            "ds_read_b64 %0, %4\n\t"
-            "ds_read_b64 %1, %4 offset:512\n\t"
-            "ds_read_b64 %2, %4 offset:1024\n\t"
-            "ds_read_b64 %3, %4 offset:1536"
-            : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3])
-            : "v"(addr)
-            : "memory");
+        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "n"(N) : "memory");
     else
-        asm volatile(
-            "ds_read_b64 %0, %2\n\t"
-            "ds_read_b64 %1, %2 offset:512"
-            : "=&v"(w[0]), "=&v"(w[1])
-            : "v"(addr)
-            : "memory");
+        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(w[0]), "+v"(w[1]) : "n"(N) : "memory");
 }
 
 // One group's contribution to the wave's D trials: rec[d] = LDS byte offset (slot area
@@ -341,22 +310,22 @@ __device__ __forceinline__ void group_trials(f32x2 (&acc)[C::D][C::J], const Rec
 {
     constexpr int D = C::D, J = C::J;
     double w[4][J];
-    issue_window<J>(w[0], base + rec[0]);
-    issue_window<J>(w[1], base + rec[1]);
-    issue_window<J>(w[2], base + rec[2]);
+    prefetch_window<J>(w[0], base + rec[0]);
+    prefetch_window<J>(w[1], base + rec[1]);
+    prefetch_window<J>(w[2], base + rec[2]);
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-        if (d + 3 < D) issue_window<J>(w[(d + 3) & 3], base + rec[d + 3]);
+        if (d + 3 < D) prefetch_window<J>(w[(d + 3) & 3], base + rec[d + 3]);
         double(&wd)[J] = w[d & 3];
         const int ahead = D - 1 - d < 3 ? D - 1 - d : 3;
         if (ahead == 3)
-            wait_window_n<J, 3 * J>(wd);
+            wait_lgkm<3 * J>(wd);
         else if (ahead == 2)
-            wait_window_n<J, 2 * J>(wd);
+            wait_lgkm<2 * J>(wd);
         else if (ahead == 1)
-            wait_window_n<J, J>(wd);
+            wait_lgkm<J>(wd);
         else
-            wait_window_n<J, 0>(wd);
+            wait_lgkm<0>(wd);
 #pragma unroll
         for (int m = 0; m < J; ++m) acc[d][m] += __builtin_bit_cast(f32x2, wd[m]);
         pin_accumulators(acc[d]);
@@ -373,46 +342,6 @@ __device__ __forceinline__ void group_trials(f32x2 (&acc)[C::D][C::J], const Rec
 // `hi += lo >> 8, lo &= 255` - then hi 256 + lo is the exact integer sum (< nchan 255 <
 // 2^24), converted to float32 once per item.  The u16 pairs are added as plain 32-bit words
 // (v_add_u32): each half stays below 2^16, so no carry crosses into the high half.
-
-#define PU_WAIT1_CASE(N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(w) : : "memory");
-template <int N>
-__device__ __forceinline__ void wait_window1(u32x2 &w)
-{
-    static_assert(N >= 0 && N <= 7, "lgkmcnt");
-    if constexpr (N == 7) { PU_WAIT1_CASE(7) }
-    else if constexpr (N == 6) { PU_WAIT1_CASE(6) }
-    else if constexpr (N == 5) { PU_WAIT1_CASE(5) }
-    else if constexpr (N == 4) { PU_WAIT1_CASE(4) }
-    else if constexpr (N == 3) { PU_WAIT1_CASE(3) }
-    else if constexpr (N == 2) { PU_WAIT1_CASE(2) }
-    else if constexpr (N == 1) { PU_WAIT1_CASE(1) }
-    else { PU_WAIT1_CASE(0) }
-}
-#undef PU_WAIT1_CASE
-
-// s_waitcnt lgkmcnt(N) that "defines" v (the value it guards), N in [0, 15]
-#define PU_WAITV_CASE(N) else if constexpr (N0 == N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(v) : : "memory");
-template <int N0>
-__device__ __forceinline__ void wait_lgkm(uint32_t &v)
-{
-    static_assert(N0 >= 0 && N0 <= 15, "lgkmcnt");
-    if constexpr (N0 == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) : : "memory");
-    PU_WAITV_CASE(1) PU_WAITV_CASE(2) PU_WAITV_CASE(3) PU_WAITV_CASE(4) PU_WAITV_CASE(5) PU_WAITV_CASE(6)
-    PU_WAITV_CASE(7) PU_WAITV_CASE(8) PU_WAITV_CASE(9) PU_WAITV_CASE(10) PU_WAITV_CASE(11) PU_WAITV_CASE(12)
-    PU_WAITV_CASE(13) PU_WAITV_CASE(14) PU_WAITV_CASE(15)
-}
-#undef PU_WAITV_CASE
-
-#define PU_WAIT2_CASE(N) else if constexpr (N0 == N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(v) : : "memory");
-template <int N0>
-__device__ __forceinline__ void wait_lgkm2(u32x2 &v)
-{
-    static_assert(N0 >= 0 && N0 <= 7, "lgkmcnt");
-    if constexpr (N0 == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) : : "memory");
-    PU_WAIT2_CASE(1) PU_WAIT2_CASE(2) PU_WAIT2_CASE(3) PU_WAIT2_CASE(4) PU_WAIT2_CASE(5) PU_WAIT2_CASE(6)
-    PU_WAIT2_CASE(7)
-}
-#undef PU_WAIT2_CASE
 
 // 16-bit slot build, one chunk of 128 elements: lane l's two elements 128 c + 2 l (+ 1) as
 // the byte sums of the G channels (addresses ad[q], reads rb in flight).
@@ -432,7 +361,7 @@ template <int G, int Q>
 __device__ __forceinline__ void s16_quad_step(u32x2 (&d)[G], const uint32_t (&src)[G], uint32_t &acc02, uint32_t &acc13)
 {
     if constexpr (Q < G) {
-        wait_lgkm2<G - 1 - Q>(d[Q]);
+        wait_lgkm<G - 1 - Q>(d[Q]);
         const uint32_t t = __builtin_amdgcn_alignbyte(d[Q].y, d[Q].x, src[Q]);  // bytes src .. src + 3
         acc02 += t & 0x00ff00ffu;
         acc13 += (t >> 8) & 0x00ff00ffu;
@@ -519,6 +448,20 @@ __device__ __forceinline__ void s16_run(uint32_t (&rb)[P][G][2], const uint32_t 
 }
 
 
+// The next lane's value (DPP wave_shl:1; lane 63 takes lane 0 of `next` by wave_rol:1).
+__device__ __forceinline__ uint32_t s16_nextlane(uint32_t v, uint32_t next)
+{
+    const uint32_t x = (uint32_t)__builtin_amdgcn_mov_dpp((int)next, 0x134, 0xf, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)v, 0x130, 0xf, 0xf, false);
+}
+
+// The odd-shifted u16 pair (R[2k + 1], R[2k + 2]) of lane k: the high half of its pair e =
+// (R[2k], R[2k + 1]) with the low half of the next lane's (lane 63: of enext's lane 0).
+__device__ __forceinline__ uint32_t s16_odd(uint32_t e, uint32_t enext)
+{
+    return __builtin_amdgcn_alignbit(s16_nextlane(e, enext), e, 16);
+}
+
 __device__ __forceinline__ void issue_window1(u32x2 &w, uint32_t addr)
 {
     asm volatile("ds_read_b64 %0, %1" : "=&v"(w) : "v"(addr) : "memory");
@@ -533,7 +476,7 @@ __device__ __forceinline__ void trials16_step(uint32_t (&lo)[D][2], u32x2 (&w)[A
         if constexpr (I + A < D) issue_window1(w[(I + A) % (A + 1)], base + rec[I + A]);
         constexpr int ahead = D - 1 - I < A ? D - 1 - I : A;
         u32x2 &wd = w[I % (A + 1)];
-        wait_window1<ahead>(wd);
+        wait_lgkm<ahead>(wd);
         lo[I][0] += wd.x;  // two u16 sums per dword: no carry crosses (each half < 2^16)
         lo[I][1] += wd.y;
         asm volatile("" : "+v"(lo[I][0]), "+v"(lo[I][1]));
@@ -886,11 +829,6 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
     auto slot16_pairs = [&](const meta_t &m) {
         const bool four = m[0] > 384;
         const int copy_bytes = copy_bytes_of(m[0]);
-        auto odd = [&](uint32_t e, uint32_t enext) {  // (R[2k + 1], R[2k + 2]) of lane k
-            const uint32_t x = (uint32_t)__builtin_amdgcn_mov_dpp((int)enext, 0x134, 0xf, 0xf, false);  // wave_rol:1
-            const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)e, 0x130, 0xf, 0xf, false);  // wave_shl:1
-            return __builtin_amdgcn_alignbit(y, e, 16);
-        };
         // per channel the lane's byte address; 2 G byte reads per chunk (ds_read_u8 in inline
         // asm: the order kept by s16_run holds ~15 in flight in 16 registers - each value is
         // added, then its register takes the read of chunk c + 8 / G, same channel and byte)
@@ -908,7 +846,7 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
             s16_run<G, P, 0, 3>(rb, ad, e);
         }
         const uint32_t e0 = e[0], e1 = e[1], e2 = e[2], e3 = e[3];
-        uint32_t o0 = odd(e0, e1), o1 = odd(e1, e2), o2 = odd(e2, e3), o3 = four ? odd(e3, e3) : 0u;
+        uint32_t o0 = s16_odd(e0, e1), o1 = s16_odd(e1, e2), o2 = s16_odd(e2, e3), o3 = four ? s16_odd(e3, e3) : 0u;
         asm volatile("" : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3));
         const uint32_t c0 = lds_base + (uint32_t)m[1];
         const uint32_t cbu = (uint32_t)copy_bytes;
@@ -933,16 +871,6 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
     auto slot16_quad = [&](const meta_t &m) {
         const int len = m[0];  // 256 (= TT) .. 510
         const int copy_bytes = copy_bytes_of(len);
-        auto odd = [&](uint32_t e, uint32_t enext) {  // (R[2k + 1], R[2k + 2]) of lane k
-            const uint32_t x = (uint32_t)__builtin_amdgcn_mov_dpp((int)enext, 0x134, 0xf, 0xf, false);  // wave_rol:1
-            const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)e, 0x130, 0xf, 0xf, false);  // wave_shl:1
-            return __builtin_amdgcn_alignbit(y, e, 16);
-        };
-        // the next lane's value (lane 63: lane 0 of `next`)
-        auto nextlane = [&](uint32_t v, uint32_t next) {
-            const uint32_t x = (uint32_t)__builtin_amdgcn_mov_dpp((int)next, 0x134, 0xf, 0xf, false);
-            return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)v, 0x130, 0xf, 0xf, false);
-        };
         // elements 0 .. 255: four per lane (s16_quad)
         uint32_t src[G];
 #pragma unroll
@@ -968,8 +896,8 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
         // dword j of copy s: copy 0 E[j], copy 1 O[j], copy 2 E[j + 1], copy 3 O[j + 1]
         // (E[k] = (R[2k], R[2k+1]), O[k] = (R[2k+1], R[2k+2])); lane l of the first 256
         // elements owns dwords 2l and 2l + 1: E[2l] = ea, E[2l+1] = eb
-        const uint32_t nea = nextlane(ea, e[2]);  // E[2l + 2] (lane 63: the tail's first pair)
-        const uint32_t neb = nextlane(eb, e[2]);  // E[2l + 3] (lane 63's is rewritten by the tail)
+        const uint32_t nea = s16_nextlane(ea, e[2]);  // E[2l + 2] (lane 63: the tail's first pair)
+        const uint32_t neb = s16_nextlane(eb, e[2]);  // E[2l + 3] (lane 63's is rewritten by the tail)
         u32x2 w0 = {ea, eb}, w2 = {eb, nea};
         u32x2 w1 = {__builtin_amdgcn_alignbit(eb, ea, 16), __builtin_amdgcn_alignbit(nea, eb, 16)};
         u32x2 w3 = {w1.y, __builtin_amdgcn_alignbit(neb, nea, 16)};
@@ -985,7 +913,7 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
             // first part's stores: its copy-3 dword 127 is rewritten here); a chunk reaching
             // past its copy (copies hold TT + span + 2 elements rounded to 64) stores only its
             // lanes inside it (elements 128 c + 2 l <= copy - 2)
-            const uint32_t o2 = odd(e[2], e[3]), o3 = odd(e[3], e[3]);
+            const uint32_t o2 = s16_odd(e[2], e[3]), o3 = s16_odd(e[3], e[3]);
             const bool in2 = 768u <= cbu || 512 + 4 * lane <= (int)cbu - 4;
             const bool in3 = t3 && (1024u <= cbu || 768 + 4 * lane <= (int)cbu - 4);
             auto store = [&](uint32_t base, uint32_t v2, uint32_t v3) {
@@ -1209,292 +1137,6 @@ dedisp_sub_kernel(SubArgs a, const i32x4 *__restrict__ tiles, const i32x2 *__res
                                             pu::xcd_remap(blockIdx.x, gridDim.x), true);
 }
 
-// Certification state at the workspace tail (pu_plan_workspace_bytes), then the list
-// of the trials to recompute (int32 each).
-struct CertState {
-    int32_t nflag;       // trials the fast path could not certify (listed after the state)
-    int32_t nnonfinite;  // of which: a non-finite partial (NaN / inf in the series)
-    int32_t scan;        // non-finite input scan (pu::nonfinite_any_async)
-    int32_t why[3];      // flagged by: std not above its bound, S/N sign, S/N tie
-    int32_t pad[58];
-};
-static_assert(sizeof(CertState) == 256, "CertState");
-
-// Rounding model of one plan's fast statistics.
-struct CertModel {
-    int32_t tie_check;  // the series is exact (u8 with exact f32 sums, any f64 accumulation)
-    double e_rel;       // per-sample series error bound / (|mean| + 4 std + |max|)
-    double gamma;       // relative rounding of the epilogue's sums of (shifted) squares
-};
-
-// One workgroup per trial: combine the per-time-tile partials in a fixed order
-// (thread-strided then an LDS tree: deterministic), then the reference's S/N logic
-// (dedispersion.py:186-201): snr_w = max(reb_w)/std(reb_w), first strict best.
-// Certification: a trial whose statistics or S/N decisions the fast path's summation
-// order could change is appended to the list in ``cert`` (the host recomputes it
-// exactly).  Bounds: the epilogue's sums of squares carry relative error gamma of
-// Q = their magnitude (tile-local second moments + recentring terms), so
-// |d var| <= 4 gamma Q; a per-sample series error E moves a width-w std by <= w E and
-// max - w mean by <= 2 w E.  A trial is flagged when a partial is non-finite, when
-// std is not > 4 x its bound (zero or rounding-level std: constant inputs), when
-// max - w mean is within its bound of 0 (the S/N sign decision), and - for plans whose
-// series is exact - when two S/N values of the strict first-best chain are within the
-// sum of their bounds (ties).
-template <typename PT>
-__global__ void __launch_bounds__(256)
-pu_finalize_kernel(const PT *__restrict__ part, int ntt, int n, int tt_len,
-                   double *max_out, double *std_out, double *snr_out, int32_t *win_out,
-                   CertModel cm, CertState *cert, int32_t *list, int first)
-{
-    __shared__ double red[4][4][256];
-    const int trial = first + (int)blockIdx.x;  // trials [first, first + gridDim.x) of the plan
-    const int tid = threadIdx.x;
-    const PT *p = part + (size_t)trial * ntt * kPartStride;
-    const double mu = p[0];
-    double S1[4] = {0, 0, 0, 0}, S2[4] = {0, 0, 0, 0}, MX[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    double A2[4] = {0, 0, 0, 0};
-    for (int i = tid; i < ntt; i += 256) {
-        const PT *q = p + (size_t)i * kPartStride;
-        const double dk = q[0] - mu;
-        for (int w = 0; w < 4; ++w) {
-            const int width = 1 << w;
-            const long lo = (long)i * tt_len / width;
-            const long hi = min((long)(i + 1) * tt_len / width, (long)(n / width));
-            const double cntb = (double)max(0L, hi - lo);
-            if (cntb <= 0) continue;
-            const double s1 = q[2 + 3 * w], s2 = q[3 + 3 * w];
-            const double wd = width * dk;
-            S1[w] += s1 + cntb * wd;
-            S2[w] += s2 + 2.0 * wd * s1 + cntb * wd * wd;
-            // magnitude the rounding bound scales with: the tile's sum of squares (relative
-            // error gamma), its recentring term through s1 (|d s1| <= gamma sum|y| <=
-            // gamma sqrt(cnt s2)), and 2^-30 of the float64 recentring square
-            A2[w] += fabs(s2) + 2.0 * fabs(wd) * sqrt(cntb * fabs(s2)) + 0x1p-30 * cntb * wd * wd;
-            // NaN-propagating (a NaN partial max makes the trial non-finite below)
-            MX[w] = (q[1 + 3 * w] > MX[w] || q[1 + 3 * w] != q[1 + 3 * w]) ? q[1 + 3 * w] : MX[w];
-        }
-    }
-    for (int w = 0; w < 4; ++w) {
-        red[0][w][tid] = S1[w];
-        red[1][w][tid] = S2[w];
-        red[2][w][tid] = MX[w];
-        red[3][w][tid] = A2[w];
-    }
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            for (int w = 0; w < 4; ++w) {
-                red[0][w][tid] += red[0][w][tid + s];
-                red[1][w][tid] += red[1][w][tid + s];
-                const double a = red[2][w][tid], b = red[2][w][tid + s];
-                red[2][w][tid] = (b > a || b != b) ? b : a;
-                red[3][w][tid] += red[3][w][tid + s];
-            }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const double mean = mu + red[0][0][0] / n;  // mean of the dedispersed series
-        double best = 0.0;
-        int bestw = 0;
-        double sdw[4] = {0, 0, 0, 0}, Qw[4] = {0, 0, 0, 0};
-        bool nonfinite = !isfinite(mu) || !isfinite(mean);
-        for (int w = 0; w < 4; ++w) {
-            const int width = 1 << w;
-            const long nb = n / width;
-            if (nb <= 0) continue;
-            const double m1 = red[0][w][0] / nb;
-            const double var = red[1][w][0] / nb - m1 * m1;
-            const double sd = sqrt(var > 0 ? var : 0.0);
-            sdw[w] = sd;
-            Qw[w] = red[3][w][0] / nb;
-            nonfinite = nonfinite || !isfinite(red[0][w][0]) || !isfinite(red[1][w][0]) ||
-                        !isfinite(red[2][w][0]) || !isfinite(red[3][w][0]);
-            const double snr = (red[2][w][0] - width * mean) / sd;
-            if (snr > best) {
-                best = snr;
-                bestw = width;
-            }
-        }
-        bool uncertain = false;
-        int why = -1;
-        if (!nonfinite) {
-            const double E = cm.e_rel * (fabs(mean) + 4.0 * sdw[0] + fabs(red[2][0][0]));
-            double b = 0.0, eb = 0.0;  // the reference's (best_snr, its bound) chain
-            for (int w = 0; w < 4 && !uncertain; ++w) {
-                const int width = 1 << w;
-                if (n / width <= 0) continue;
-                const double sd = sdw[w], MXw = red[2][w][0];
-                const double e_var = 4.0 * cm.gamma * Qw[w];
-                const double e_sd = sd > 0 ? e_var / sd + width * E : INFINITY;
-                const double num = MXw - width * mean;
-                // max - w mean: the series error, the mean's rounding (through S1), the
-                // float64 combination, and - unless the rebinned sums are exact (exact-series
-                // plans: integers < 2^24 or float64) - their float32 rounding
-                const double e_num = 2.0 * width * E + cm.gamma * width * sqrt(Qw[0]) +
-                                     (cm.tie_check ? 0.0 : cm.gamma * fabs(MXw)) +
-                                     0x1p-50 * (fabs(MXw) + width * fabs(mean));
-                if (!(e_sd <= 0.25 * sd) || !(fabs(num) > e_num)) {
-                    uncertain = true;
-                    why = !(e_sd <= 0.25 * sd) ? 0 : 1;
-                    break;
-                }
-                const double snr = num / sd;
-                const double e_snr = (e_num + fabs(snr) * e_sd) / (sd - e_sd) + 0x1p-44 * fabs(snr);
-                if (cm.tie_check) {
-                    const double d = snr - b;
-                    if (!(fabs(d) > e_snr + eb)) {
-                        uncertain = true;
-                        why = 2;
-                    } else if (d > 0) {
-                        b = snr;
-                        eb = e_snr;
-                    }
-                }
-            }
-        }
-        if (nonfinite || uncertain) {
-            list[atomicAdd(&cert->nflag, 1)] = trial;
-            if (nonfinite) atomicAdd(&cert->nnonfinite, 1);
-            if (why >= 0) atomicAdd(&cert->why[why], 1);
-        }
-        max_out[trial] = red[2][0][0] - mean;
-        std_out[trial] = sdw[0];
-        snr_out[trial] = best;
-        win_out[trial] = bestw;
-    }
-}
-
-// An owning device pointer (move-only): the one place a plan table is freed.
-template <typename T>
-struct DevicePtr {
-    T *ptr = nullptr;
-    DevicePtr() = default;
-    DevicePtr(DevicePtr &&o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
-    DevicePtr &operator=(DevicePtr &&o) noexcept
-    {
-        std::swap(ptr, o.ptr);
-        return *this;
-    }
-    ~DevicePtr() { (void)hipFree(ptr); }
-    operator T *() const { return ptr; }
-};
-
-// The plan's tables in device memory.
-struct DeviceTables {
-    DevicePtr<int32_t> first, count, rowlen, base, slots;
-    DevicePtr<u32x4> rec;
-    DevicePtr<uint32_t> rec8, recs;
-    DevicePtr<i32x4> tiles, stages;
-    DevicePtr<i32x2> tile_stages;
-
-    // Uploads every table the plan's mode fills, the padded slot records included, and
-    // releases each host copy.
-    int upload(PlanTables &t)
-    {
-        pad_slots(t);
-        int rc = PU_OK;
-        auto put = [&rc](auto &dst, auto &vec) {
-            if (rc || vec.empty()) return;
-            const size_t bytes = vec.size() * sizeof vec[0];
-            rc = pu::hip_check(hipMalloc((void **)&dst.ptr, std::max<size_t>(bytes, 16)), "hipMalloc(plan)");
-            if (rc) return;
-            rc = pu::hip_check(hipMemcpy(dst.ptr, vec.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(plan)");
-            std::remove_reference_t<decltype(vec)>().swap(vec);
-        };
-        put(first, t.first);
-        put(count, t.count);
-        put(rowlen, t.rowlen);
-        put(tiles, t.tiles);
-        put(tile_stages, t.tile_stages);
-        put(stages, t.stages);
-        put(slots, t.slots);
-        put(recs, t.recs);
-        put(base, t.base);
-        put(rec, t.rec);
-        put(rec8, t.rec8);
-        return rc;
-    }
-};
-
-}  // namespace
-
-// A plan: the problem, what the planner made of it, the device tables and the per-call
-// state (timing events and the launch counter, the pinned certification copy and the last
-// call's certification outcome).  Cached plans are shared across threads (ctypes releases
-// the GIL): every entry point that launches or reads the per-call state holds the lock
-// for the whole call.
-struct pu_plan {
-    mutable std::mutex lock;
-    PlanProblem pb;
-    PlanTables t;
-    DeviceTables d;
-    // optional kernel timing: events before the first and after the last launch of
-    // each dispatch
-    std::vector<hipEvent_t> ev_start, ev_stop;
-    int64_t launches = 0;
-    uint64_t *d_stamps = nullptr;  // diagnostic build (PU_STAMPS): phase-cycle totals
-    // certification: the shift table (host) for exact recomputation of
-    // flagged trials, a pinned copy of the device CertState, the last call's outcome
-    std::vector<int64_t> shifts;
-    CertState *h_cert = nullptr;
-    int64_t cert_rechecked = 0, cert_nan = 0, cert_why[3] = {0, 0, 0}, cert_us = 0;
-};
-
-namespace {
-
-template <typename Kern>
-int ensure_lds(Kern kern, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return PU_OK;
-    return pu::hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
-                         "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-}
-
-// dedisp_f64_kernel (dedisp_f64.hip, its own translation unit and code-generation options)
-int launch_f64(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s, bool tin_f32)
-{
-    // records, then the first-window table (planner: one upload)
-    const uint32_t *first_off = p->d.rec8 + (size_t)p->t.ndt * p->pb.nchan * kTPT / 2;
-    return pu_dd_launch_f64(tin_f32, plane, &a, sizeof a, p->t.lds_bytes, p->d.first, p->d.count, p->d.rowlen,
-                            p->d.base, p->d.rec8, first_off, s, kF64Waves);
-}
-
-template <typename Tin, typename Tl, typename Ta>
-int launch_variant(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
-{
-    const dim3 grid((unsigned)((int64_t)a.ndt * a.ntt_run)), block(kThreads);
-    if (plane) {
-        auto kern = dedisp_kernel<Tin, Tl, Ta, true, false>;
-        int rc = ensure_lds(kern, p->t.lds_bytes);
-        if (rc) return rc;
-        hipLaunchKernelGGL(kern, grid, block, p->t.lds_bytes, s, a, p->d.first, p->d.count, p->d.rowlen, p->d.base,
-                           p->d.rec);
-    } else {
-        auto kern = dedisp_kernel<Tin, Tl, Ta, false, true>;
-        int rc = ensure_lds(kern, p->t.lds_bytes);
-        if (rc) return rc;
-        hipLaunchKernelGGL(kern, grid, block, p->t.lds_bytes, s, a, p->d.first, p->d.count, p->d.rowlen, p->d.base,
-                           p->d.rec);
-    }
-    return pu::launch_check("dedisp_kernel");
-}
-
-int dispatch_variant(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
-{
-    switch (p->pb.variant) {
-    case V_U8_F32: return launch_variant<uint8_t, float, float>(p, a, plane, s);
-    case V_F32_F32: return launch_variant<float, float, float>(p, a, plane, s);
-    case V_F64_F64: return launch_f64(p, a, plane, s, false);
-    case V_U8_F64: return launch_variant<uint8_t, float, double>(p, a, plane, s);
-    case V_F32_F64: return launch_f64(p, a, plane, s, true);
-    case V_F64_F32: return launch_variant<double, float, float>(p, a, plane, s);
-    }
-    pu::set_error("bad plan variant");
-    return PU_EINVAL;
-}
-
 template <class C, typename Tin, int G>
 int launch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
 {
@@ -1519,7 +1161,7 @@ int launch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
     const int64_t nblk = nitems;
     const dim3 grid((unsigned)nblk), block(C::THREADS);
     auto go = [&](auto kern) {
-        int rc = ensure_lds(kern, p->t.lds_bytes);
+        int rc = pu::ensure_lds(kern, p->t.lds_bytes);
         if (rc) return rc;
         hipLaunchKernelGGL(kern, grid, block, p->t.lds_bytes, s, sa, p->d.tiles, p->d.tile_stages, p->d.stages,
                            p->d.slots, p->d.base, p->d.recs);
@@ -1557,8 +1199,13 @@ int launch_sub_shape(const pu_plan *p, const DedispArgs &a, bool plane, hipStrea
     return with_shape(p->t.shape, [&](auto c) { return launch_sub_g<decltype(c), Tin>(p, a, plane, s); });
 }
 
-int dispatch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
+}  // namespace
+
+int pu_dd_launch_sub(const pu_plan *p, const void *args, size_t args_bytes, bool plane, void *stream)
 {
+    PU_REQUIRE(args_bytes == sizeof(DedispArgs), "pu_dd_launch_sub: argument block size mismatch");
+    const DedispArgs &a = *reinterpret_cast<const DedispArgs *>(args);
+    hipStream_t s = pu::as_stream(stream);
     switch (p->pb.dtype) {
     case PU_U8: return launch_sub_shape<uint8_t>(p, a, plane, s);
     case PU_F32: return launch_sub_shape<float>(p, a, plane, s);
@@ -1567,535 +1214,3 @@ int dispatch_sub(const pu_plan *p, const DedispArgs &a, bool plane, hipStream_t 
     pu::set_error("bad plan dtype");
     return PU_EINVAL;
 }
-
-int dispatch(pu_plan *p, const DedispArgs &a, bool plane, hipStream_t s)
-{
-    const size_t nslot = p->ev_start.size();
-    const size_t slot = nslot ? (size_t)(p->launches % (int64_t)nslot) : 0;
-    if (nslot) PU_TRY_HIP(hipEventRecord(p->ev_start[slot], s));
-    int rc = p->t.group > 1 ? dispatch_sub(p, a, plane, s) : dispatch_variant(p, a, plane, s);
-    if (rc) return rc;
-    if (nslot) PU_TRY_HIP(hipEventRecord(p->ev_stop[slot], s));
-    ++p->launches;
-    return PU_OK;
-}
-
-void destroy_events(pu_plan *p)
-{
-    for (auto *v : {&p->ev_start, &p->ev_stop}) {
-        for (auto e : *v) (void)hipEventDestroy(e);
-        v->clear();
-    }
-}
-
-void free_plan(pu_plan *p)
-{
-    if (!p) return;
-    destroy_events(p);
-    (void)hipFree(p->d_stamps);
-    if (p->h_cert) (void)hipHostFree(p->h_cert);
-    delete p;  // the device tables: ~DeviceTables
-}
-
-// The plan keeps its shift table (host) for the exact recomputation of flagged trials,
-// and a pinned copy of the certification state.
-int finish_plan(pu_plan *p, const int64_t *shifts)
-{
-    p->shifts.assign(shifts, shifts + p->pb.ndm * p->pb.nchan);
-    return pu::hip_check(hipHostMalloc((void **)&p->h_cert, sizeof(CertState), hipHostMallocDefault),
-                         "hipHostMalloc(cert)");
-}
-
-// the plan's partial records (part_elem: dedisp_plan.h), in whole 256-byte pieces
-size_t part_bytes(const pu_plan *p) { return ((size_t)p->pb.ndm * p->t.ntt * kPartStride * part_elem(p->pb) + 255) & ~size_t(255); }
-
-// Rounding model of the plan's fast statistics (pu_finalize_kernel).
-CertModel cert_model(const pu_plan *p)
-{
-    CertModel m{};
-    if (kVariants[p->pb.variant].acc_f64) {
-        m.tie_check = 1;  // float64 channel order: the reference's series bit for bit
-        m.e_rel = 0x1p-50;
-        m.gamma = 0x1p-44;
-    } else if (p->pb.dtype == PU_U8 && 8 * 255 * p->pb.nchan < (int64_t(1) << 24)) {
-        // integer sums (and their 8-sample rebins) below 2^24: exact in float32.  The
-        // epilogue's sums of squares: <= 14 float32 roundings of nonnegative terms (the
-        // shifted value, the square-and-add, 4 lane-local adds, the pair add, 2 permlane
-        // and 4 row-reduction adds, the float record) = 14 x 2^-24 < 2^-20
-        m.tie_check = 1;
-        m.e_rel = 0.0;
-        m.gamma = 0x1p-20;
-    } else {
-        // float32 sums of float data: the typical (random-walk) rounding of nchan terms
-        // with an 8x margin, relative to the series' magnitude; S/N ties within the
-        // float32 tolerance are not recomputed (the stated tolerance covers them)
-        m.tie_check = 0;
-        m.e_rel = 8.0 * 0x1p-24 * std::sqrt((double)p->pb.nchan);
-        m.gamma = 0x1p-19;
-    }
-    return m;
-}
-
-// cleared: the caller already zeroed the certification state earlier in the stream.
-// Trials [first, first + count) (count < 0: every trial); outputs indexed by plan trial.
-int launch_finalize(pu_plan *p, const void *part, double *mx, double *sd, double *snr, int32_t *win, char *ws,
-                    hipStream_t s, bool cleared = false, int64_t first = 0, int64_t count = -1)
-{
-    CertState *cert = reinterpret_cast<CertState *>(ws + part_bytes(p));
-    int32_t *list = reinterpret_cast<int32_t *>(cert + 1);
-    if (!cleared) PU_TRY_HIP(hipMemsetAsync(cert, 0, sizeof(CertState), s));
-    if (count < 0) count = p->pb.ndm - first;
-    if (count == 0) return PU_OK;
-    if (part_elem(p->pb) == sizeof(float))
-        hipLaunchKernelGGL(pu_finalize_kernel<float>, dim3((unsigned)count), dim3(256), 0, s,
-                           reinterpret_cast<const float *>(part), p->t.ntt, (int)p->pb.n, p->t.TT, mx, sd, snr, win, cert_model(p),
-                           cert, list, (int)first);
-    else
-        hipLaunchKernelGGL(pu_finalize_kernel<double>, dim3((unsigned)count), dim3(256), 0, s,
-                           reinterpret_cast<const double *>(part), p->t.ntt, (int)p->pb.n, p->t.TT, mx, sd, snr, win, cert_model(p),
-                           cert, list, (int)first);
-    return pu::launch_check("pu_finalize_kernel");
-}
-
-// After the finalize kernel: wait for it, then settle the flagged trials.  An input
-// holding NaN / inf (found by a scan, run only when some trial saw a non-finite value)
-// gives every trial the reference's NaN result; other flagged trials are recomputed
-// exactly - their float64 channel-order series (the reference's bit for bit, by a direct
-// gather: ~1 ms per trial at C3, far below a channel-mode sub-plan's cost for the
-// few trials a search flags) + pu_series_stats - in batches that fit ~1 GiB of
-// stream-ordered scratch allocated for the call.
-int resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, double *sd, double *snr, int32_t *win,
-                    char *ws, hipStream_t s, int64_t first = 0, int64_t count = -1)
-{
-    if (count < 0) count = p->pb.ndm - first;
-    CertState *cert = reinterpret_cast<CertState *>(ws + part_bytes(p));
-    const int32_t *list = reinterpret_cast<const int32_t *>(cert + 1);
-    p->cert_rechecked = 0;
-    p->cert_nan = 0;
-    PU_TRY_HIP(hipMemcpyAsync(p->h_cert, cert, sizeof(CertState), hipMemcpyDeviceToHost, s));
-    PU_TRY_HIP(hipStreamSynchronize(s));
-    const int64_t nflag = p->h_cert->nflag;
-    for (int k = 0; k < 3; ++k) p->cert_why[k] = p->h_cert->why[k];
-    p->cert_us = 0;
-    if (nflag == 0) return PU_OK;
-    const auto t_start = std::chrono::steady_clock::now();
-    struct Timer {  // host time spent settling the flagged trials (pu_plan_info cert_us)
-        pu_plan *p;
-        std::chrono::steady_clock::time_point t0;
-        ~Timer()
-        {
-            p->cert_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0)
-                             .count();
-        }
-    } timer{p, t_start};
-    if (p->h_cert->nnonfinite > 0 && p->pb.dtype != PU_U8) {
-        int rc = pu::nonfinite_any_async(data, p->pb.dtype, p->pb.nchan, p->pb.n, ld, &cert->scan, s);
-        if (rc) return rc;
-        PU_TRY_HIP(hipMemcpyAsync(p->h_cert, cert, sizeof(CertState), hipMemcpyDeviceToHost, s));
-        PU_TRY_HIP(hipStreamSynchronize(s));
-        if (p->h_cert->scan) {
-            // every trial's series holds every input sample once (circular shift-and-sum),
-            // so a NaN / inf anywhere reaches every trial: np.mean -> NaN or inf, the
-            // shifted series -> NaN, max = std = NaN, no S/N beats 0 (dedispersion.py:186-201)
-            p->cert_nan = 1;
-            int rc2 = pu::nan_rule(count, mx + first, sd + first, snr + first, win + first, s);
-            if (rc2) return rc2;
-            PU_TRY_HIP(hipStreamSynchronize(s));
-            return PU_OK;
-        }
-    }
-    std::vector<int32_t> idx((size_t)nflag);
-    PU_TRY_HIP(hipMemcpyAsync(idx.data(), list, (size_t)nflag * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PU_TRY_HIP(hipStreamSynchronize(s));
-    std::sort(idx.begin(), idx.end());
-    const int64_t n = p->pb.n, nchan = p->pb.nchan;
-    const int64_t per_row = n * 8 + (int64_t)pu_series_stats_workspace_bytes(1, n) + nchan * 8;
-    const int64_t B = std::max<int64_t>(1, std::min<int64_t>(nflag, (int64_t(1) << 30) / per_row));
-    const size_t plane_b = ((size_t)B * n * sizeof(double) + 255) & ~size_t(255);
-    const size_t sws_b = (pu_series_stats_workspace_bytes(B, n) + 255) & ~size_t(255);
-    const size_t sh_b = ((size_t)B * nchan * sizeof(int64_t) + 255) & ~size_t(255);
-    const size_t need = plane_b + sws_b + sh_b + (size_t)B * sizeof(int32_t);
-    // per-call scratch, stream-ordered (no device-wide synchronisation, nothing held
-    // with the plan between calls); freed on every return path
-    void *rc_buf = nullptr;
-    PU_TRY_HIP(hipMallocAsync(&rc_buf, need, s));
-    struct Scratch {
-        void *b;
-        hipStream_t s;
-        ~Scratch()
-        {
-            (void)hipFreeAsync(b, s);
-            (void)hipStreamSynchronize(s);
-        }
-    } scratch{rc_buf, s};
-    char *sc = reinterpret_cast<char *>(rc_buf);
-    double *plane = reinterpret_cast<double *>(sc);
-    void *sws = sc + plane_b;
-    int64_t *d_sh = reinterpret_cast<int64_t *>(sc + plane_b + sws_b);
-    int32_t *d_idx = reinterpret_cast<int32_t *>(sc + plane_b + sws_b + sh_b);
-    std::vector<int64_t> sh;
-    int rc = PU_OK;
-    for (int64_t i0 = 0; !rc && i0 < nflag; i0 += B) {
-        const int64_t m = std::min(B, nflag - i0);
-        sh.resize((size_t)(m * nchan));
-        for (int64_t k = 0; k < m; ++k)
-            std::copy_n(p->shifts.data() + (size_t)idx[(size_t)(i0 + k)] * nchan, nchan, sh.data() + k * nchan);
-        for (auto &v : sh) v = ((v % n) + n) % n;  // row index (t + shift) mod n
-        rc = pu::hip_check(hipMemcpyAsync(d_sh, sh.data(), sh.size() * sizeof(int64_t), hipMemcpyHostToDevice, s),
-                           "hipMemcpyAsync(recheck shifts)");
-        if (!rc) rc = pu::exact_series(data, p->pb.dtype, nchan, n, ld, d_sh, m, plane, s);
-        if (!rc)
-            rc = pu::hip_check(hipMemcpyAsync(d_idx, idx.data() + i0, (size_t)m * sizeof(int32_t),
-                                              hipMemcpyHostToDevice, s), "hipMemcpyAsync(recheck index)");
-        if (!rc) rc = pu_series_stats(plane, m, n, n, d_idx, mx, sd, snr, win, sws, sws_b, s);
-        const int rs = pu::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(recheck)");
-        if (!rc) rc = rs;
-    }
-    if (!rc) p->cert_rechecked = nflag;
-    return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pu_plan_create_ex(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t n, const int64_t *shifts,
-                      int64_t ndm, const pu_plan_opts *opts)
-{
-    PU_REQUIRE(out != nullptr, "pu_plan_create: out is NULL");
-    *out = nullptr;
-    PlanProblem pb;
-    int rc = check_plan_args(dtype, acc, nchan, n, shifts, ndm, opts, pb);
-    if (rc) return rc;
-    pu_plan *p = new pu_plan();
-    p->pb = pb;
-    rc = choose_plan(p->pb, shifts, *opts, p->t);
-    if (!rc) rc = p->d.upload(p->t);
-    if (!rc) rc = finish_plan(p, shifts);
-    if (rc) {
-        free_plan(p);
-        return rc;
-    }
-    *out = p;
-    return PU_OK;
-}
-
-int pu_plan_create_grouped(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t n, const int64_t *shifts,
-                           int64_t ndm, int group)
-{
-    pu_plan_opts o{};
-    o.group = group;
-    o.shape = -1;
-    o.u8_dma = -1;
-    o.dt_major = -1;
-    return pu_plan_create_ex(out, dtype, acc, nchan, n, shifts, ndm, &o);
-}
-
-int pu_plan_create(pu_plan **out, int dtype, int acc, int64_t nchan, int64_t n, const int64_t *shifts, int64_t ndm)
-{
-    return pu_plan_create_grouped(out, dtype, acc, nchan, n, shifts, ndm, 0);
-}
-
-void pu_plan_destroy(pu_plan *p) { free_plan(p); }
-
-int pu_plan_enable_timing(pu_plan *p, int nslots)
-{
-    PU_REQUIRE(p != nullptr && nslots >= 0 && nslots <= 65536, "pu_plan_enable_timing: bad arguments");
-    std::lock_guard<std::mutex> guard(p->lock);
-    destroy_events(p);
-    for (auto *v : {&p->ev_start, &p->ev_stop}) {
-        v->assign((size_t)nslots, nullptr);
-        for (int i = 0; i < nslots; ++i) PU_TRY_HIP(hipEventCreate(&(*v)[i]));
-    }
-    p->launches = 0;
-    return PU_OK;
-}
-
-int pu_plan_stamps(pu_plan *p, int64_t *out, int n)
-{
-    PU_REQUIRE(p != nullptr && out != nullptr, "pu_plan_stamps: bad arguments");
-    std::lock_guard<std::mutex> guard(p->lock);
-#ifdef PU_STAMPS
-    if (!p->d_stamps) {
-        PU_TRY_HIP(hipMalloc((void **)&p->d_stamps, 8 * sizeof(uint64_t)));
-        PU_TRY_HIP(hipMemset(p->d_stamps, 0, 8 * sizeof(uint64_t)));
-        return 0;  // armed: the next launches accumulate
-    }
-    uint64_t h[8];
-    PU_TRY_HIP(hipDeviceSynchronize());
-    PU_TRY_HIP(hipMemcpy(h, p->d_stamps, sizeof h, hipMemcpyDeviceToHost));
-    PU_TRY_HIP(hipMemset(p->d_stamps, 0, 8 * sizeof(uint64_t)));
-    const int m = std::min(n, 8);
-    for (int i = 0; i < m; ++i) out[i] = (int64_t)h[i];
-    return m;
-#else
-    (void)n;
-    return 0;
-#endif
-}
-
-int pu_plan_kernel_times(pu_plan *p, float *ms, int n)
-{
-    PU_REQUIRE(p != nullptr && ms != nullptr, "pu_plan_kernel_times: bad arguments");
-    std::lock_guard<std::mutex> guard(p->lock);
-    const int64_t have = std::min<int64_t>(p->launches, (int64_t)p->ev_start.size());
-    const int m = (int)std::min<int64_t>(n, have);
-    for (int i = 0; i < m; ++i) {
-        PU_TRY_HIP(hipEventSynchronize(p->ev_stop[i]));
-        PU_TRY_HIP(hipEventElapsedTime(&ms[i], p->ev_start[i], p->ev_stop[i]));
-    }
-    return m;
-}
-
-size_t pu_plan_workspace_bytes(const pu_plan *p)
-{
-    if (!p) return 0;
-    // per-(trial, time tile) partial records | CertState | flagged-trial list
-    return part_bytes(p) + sizeof(CertState) + (size_t)p->pb.ndm * sizeof(int32_t);
-}
-
-int pu_plan_info(const pu_plan *p, int64_t *info, int n)
-{
-    if (!p || !info) return 0;
-    std::lock_guard<std::mutex> guard(p->lock);
-    const int64_t cert[6] = {p->cert_rechecked, p->cert_nan, p->cert_why[0], p->cert_why[1], p->cert_why[2], p->cert_us};
-    return fill_info(p->pb, p->t, cert, info, n);
-}
-
-static int check_data(const pu_plan *p, const void *data, int64_t ld)
-{
-    PU_REQUIRE(p != nullptr, "plan is NULL");
-    PU_REQUIRE(data != nullptr, "data is NULL");
-    PU_REQUIRE(ld >= p->pb.n, "ld %lld < nsamples %lld", (long long)ld, (long long)p->pb.n);
-    PU_REQUIRE(!p->t.dma8 || (reinterpret_cast<uintptr_t>(data) % 4 == 0 && ld % 4 == 0),
-               "8-bit subband plan: rows must start on 4-byte boundaries (data %% 4 == 0, ld %% 4 == 0)");
-    return PU_OK;
-}
-
-static DedispArgs make_args(const pu_plan *p, const void *data, int64_t ld)
-{
-    DedispArgs a{};
-    a.data = data;
-    a.ld = ld;
-    a.nchan = (int32_t)p->pb.nchan;
-    a.n = (int32_t)p->pb.n;
-    a.ndt = p->t.ndt;
-    a.ntt = p->t.ntt;
-    a.tt0 = 0;
-    a.ntt_run = p->t.ntt;
-    a.ncc = p->t.ncc;
-    a.row_stride = p->t.row_stride;
-    a.small_n = p->t.small_n;
-    return a;
-}
-
-int pu_plan_search_tiles(pu_plan *p, const void *data, int64_t ld, int64_t tt_begin, int64_t tt_end,
-                         void *workspace, size_t ws_bytes, void *stream)
-{
-    int rc = check_data(p, data, ld);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(0 <= tt_begin && tt_begin <= tt_end && tt_end <= p->t.ntt,
-               "pu_plan_search_tiles: tile range [%lld, %lld) outside [0, %d)", (long long)tt_begin,
-               (long long)tt_end, p->t.ntt);
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p), "pu_plan_search_tiles: workspace too small");
-    if (tt_begin == tt_end) return PU_OK;
-    DedispArgs a = make_args(p, data, ld);
-    a.partials = workspace;
-    a.tt0 = (int32_t)tt_begin;
-    a.ntt_run = (int32_t)(tt_end - tt_begin);
-    return dispatch(p, a, false, pu::as_stream(stream));
-}
-
-int pu_plan_finalize(pu_plan *p, const void *data, int64_t ld, double *max_out, double *std_out, double *snr_out,
-                     int32_t *rebin_out, void *workspace, size_t ws_bytes, void *stream)
-{
-    int rc = check_data(p, data, ld);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(max_out && std_out && snr_out && rebin_out, "pu_plan_finalize: NULL output");
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "pu_plan_finalize: workspace too small or not 8-byte aligned");
-    hipStream_t s = pu::as_stream(stream);
-    char *ws = reinterpret_cast<char *>(workspace);
-    rc = launch_finalize(p, ws, max_out, std_out, snr_out, rebin_out, ws, s);
-    if (rc) return rc;
-    return resolve_flagged(p, data, ld, max_out, std_out, snr_out, rebin_out, ws, s);
-}
-
-int pu_plan_finalize_range(pu_plan *p, const void *data, int64_t ld, int64_t trial_begin, int64_t trial_end,
-                           double *max_out, double *std_out, double *snr_out, int32_t *rebin_out, void *workspace,
-                           size_t ws_bytes, void *stream)
-{
-    int rc = check_data(p, data, ld);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(0 <= trial_begin && trial_begin <= trial_end && trial_end <= p->pb.ndm,
-               "pu_plan_finalize_range: trial range [%lld, %lld) outside [0, %lld)", (long long)trial_begin,
-               (long long)trial_end, (long long)p->pb.ndm);
-    PU_REQUIRE(max_out && std_out && snr_out && rebin_out, "pu_plan_finalize_range: NULL output");
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "pu_plan_finalize_range: workspace too small or not 8-byte aligned");
-    hipStream_t s = pu::as_stream(stream);
-    char *ws = reinterpret_cast<char *>(workspace);
-    rc = launch_finalize(p, ws, max_out, std_out, snr_out, rebin_out, ws, s, false, trial_begin,
-                         trial_end - trial_begin);
-    if (rc) return rc;
-    return resolve_flagged(p, data, ld, max_out, std_out, snr_out, rebin_out, ws, s, trial_begin,
-                           trial_end - trial_begin);
-}
-
-int pu_plan_finalize_range_flagged(pu_plan *p, int64_t trial_begin, int64_t trial_end, double *max_out,
-                                   double *std_out, double *snr_out, int32_t *rebin_out, void *workspace,
-                                   size_t ws_bytes, int32_t *flagged, int64_t cap, int64_t *counts, void *stream)
-{
-    PU_REQUIRE(p != nullptr, "plan is NULL");
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(0 <= trial_begin && trial_begin <= trial_end && trial_end <= p->pb.ndm,
-               "pu_plan_finalize_range_flagged: trial range [%lld, %lld) outside [0, %lld)", (long long)trial_begin,
-               (long long)trial_end, (long long)p->pb.ndm);
-    PU_REQUIRE(max_out && std_out && snr_out && rebin_out && counts && (flagged || cap == 0),
-               "pu_plan_finalize_range_flagged: NULL output");
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "pu_plan_finalize_range_flagged: workspace too small or not 8-byte aligned");
-    hipStream_t s = pu::as_stream(stream);
-    char *ws = reinterpret_cast<char *>(workspace);
-    int rc = launch_finalize(p, ws, max_out, std_out, snr_out, rebin_out, ws, s, false, trial_begin,
-                             trial_end - trial_begin);
-    if (rc) return rc;
-    CertState *cert = reinterpret_cast<CertState *>(ws + part_bytes(p));
-    const int32_t *list = reinterpret_cast<const int32_t *>(cert + 1);
-    PU_TRY_HIP(hipMemcpyAsync(p->h_cert, cert, sizeof(CertState), hipMemcpyDeviceToHost, s));
-    PU_TRY_HIP(hipStreamSynchronize(s));
-    const int64_t nflag = p->h_cert->nflag;
-    counts[0] = nflag;
-    counts[1] = p->h_cert->nnonfinite;
-    for (int k = 0; k < 3; ++k) p->cert_why[k] = p->h_cert->why[k];
-    p->cert_rechecked = 0;
-    p->cert_nan = 0;
-    p->cert_us = 0;
-    const int64_t m = std::min(nflag, cap);
-    if (m > 0) {
-        PU_TRY_HIP(hipMemcpyAsync(flagged, list, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        PU_TRY_HIP(hipStreamSynchronize(s));
-        std::sort(flagged, flagged + m);
-    }
-    return PU_OK;
-}
-
-int pu_plan_exact_series(pu_plan *p, const void *data, int64_t ld, const int32_t *trials, int64_t m, int64_t t_begin,
-                         int64_t t_end, double *out, void *stream)
-{
-    int rc = check_data(p, data, ld);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(0 <= t_begin && t_begin <= t_end && t_end <= p->pb.n, "pu_plan_exact_series: samples [%lld, %lld) outside [0, %lld)",
-               (long long)t_begin, (long long)t_end, (long long)p->pb.n);
-    PU_REQUIRE(m >= 0, "pu_plan_exact_series: m < 0");
-    if (m == 0 || t_end == t_begin) return PU_OK;
-    PU_REQUIRE(trials && out, "pu_plan_exact_series: NULL trials / out");
-    const int64_t n = p->pb.n, nchan = p->pb.nchan;
-    std::vector<int64_t> sh((size_t)(m * nchan));
-    for (int64_t k = 0; k < m; ++k) {
-        PU_REQUIRE(0 <= trials[k] && trials[k] < p->pb.ndm, "pu_plan_exact_series: trial %d outside [0, %lld)",
-                   trials[k], (long long)p->pb.ndm);
-        std::copy_n(p->shifts.data() + (size_t)trials[k] * nchan, nchan, sh.data() + k * nchan);
-    }
-    for (auto &v : sh) v = ((v % n) + n) % n;
-    hipStream_t s = pu::as_stream(stream);
-    void *d_sh = nullptr;
-    PU_TRY_HIP(hipMallocAsync(&d_sh, sh.size() * sizeof(int64_t), s));
-    rc = pu::hip_check(hipMemcpyAsync(d_sh, sh.data(), sh.size() * sizeof(int64_t), hipMemcpyHostToDevice, s),
-                       "hipMemcpyAsync(exact series shifts)");
-    if (!rc)
-        rc = pu::exact_series(data, p->pb.dtype, nchan, n, ld, reinterpret_cast<const int64_t *>(d_sh), m, out, s, t_begin,
-                              t_end - t_begin);
-    (void)hipFreeAsync(d_sh, s);
-    const int rs = pu::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(exact series)");
-    return rc ? rc : rs;
-}
-
-int pu_nonfinite_any(const void *data, int dtype, int64_t nrows, int64_t ncols, int64_t ld, int32_t *flag, void *stream)
-{
-    PU_REQUIRE(data && flag, "pu_nonfinite_any: NULL pointer");
-    PU_REQUIRE(nrows >= 0 && ncols >= 0 && ld >= ncols, "pu_nonfinite_any: bad shape");
-    hipStream_t s = pu::as_stream(stream);
-    if (nrows == 0 || ncols == 0) {
-        PU_TRY_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
-        return PU_OK;
-    }
-    return pu::nonfinite_any_async(data, dtype, nrows, ncols, ld, flag, s);
-}
-
-int pu_plan_search(pu_plan *p, const void *data, int64_t ld, double *max_out, double *std_out,
-                   double *snr_out, int32_t *rebin_out, void *workspace, size_t ws_bytes, void *stream)
-{
-    int rc = check_data(p, data, ld);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(max_out && std_out && snr_out && rebin_out, "pu_plan_search: NULL output");
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "pu_plan_search: workspace too small or not 8-byte aligned");
-    DedispArgs a = make_args(p, data, ld);
-    a.partials = workspace;
-    hipStream_t s = pu::as_stream(stream);
-    char *ws = reinterpret_cast<char *>(workspace);
-    // the certification state is cleared BEFORE the search kernel: the fill then runs while
-    // the stream is idle after the previous call's host read, instead of between the search
-    // and finalize kernels (C5: ~10 us of fill + dispatch gap on the step)
-    PU_TRY_HIP(hipMemsetAsync(ws + part_bytes(p), 0, sizeof(CertState), s));
-    rc = dispatch(p, a, false, s);
-    if (rc) return rc;
-    rc = launch_finalize(p, a.partials, max_out, std_out, snr_out, rebin_out, ws, s, true);
-    if (rc) return rc;
-    return resolve_flagged(p, data, ld, max_out, std_out, snr_out, rebin_out, ws, s);
-}
-
-int pu_plan_dedisperse(pu_plan *p, const void *data, int64_t ld, void *plane, int64_t ld_plane, void *stream)
-{
-    int rc = check_data(p, data, ld);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(plane != nullptr, "pu_plan_dedisperse: plane is NULL");
-    PU_REQUIRE(ld_plane >= p->pb.n, "pu_plan_dedisperse: ld_plane < nsamples");
-    DedispArgs a = make_args(p, data, ld);
-    a.plane = plane;
-    a.ld_plane = ld_plane;
-    return dispatch(p, a, true, pu::as_stream(stream));
-}
-
-int pu_plan_dm_tiles(const pu_plan *p, int32_t *first, int32_t *count, int n)
-{
-    if (!p) return 0;
-    std::lock_guard<std::mutex> guard(p->lock);
-    const int ndt = (int)p->t.tile_first.size();
-    for (int t = 0; t < std::min(n, ndt); ++t) {
-        if (first) first[t] = p->t.tile_first[t];
-        if (count) count[t] = p->t.tile_count[t];
-    }
-    return ndt;
-}
-
-int pu_plan_dedisperse_dm_tile(pu_plan *p, const void *data, int64_t ld, int64_t dt, void *plane, int64_t ld_plane,
-                               void *stream)
-{
-    int rc = check_data(p, data, ld);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> guard(p->lock);
-    PU_REQUIRE(plane != nullptr, "pu_plan_dedisperse_dm_tile: plane is NULL");
-    PU_REQUIRE(ld_plane >= p->pb.n, "pu_plan_dedisperse_dm_tile: ld_plane < nsamples");
-    PU_REQUIRE(0 <= dt && dt < (int64_t)p->t.tile_first.size(), "pu_plan_dedisperse_dm_tile: DM tile %lld outside [0, %d)",
-               (long long)dt, (int)p->t.tile_first.size());
-    DedispArgs a = make_args(p, data, ld);
-    a.dt0 = (int32_t)dt;
-    a.ndt = 1;
-    // the kernels write trial row (first + i) at plane + (first + i) ld_plane: shift the base
-    // so that the tile's rows land at rows 0 .. count - 1 of the caller's plane
-    const size_t elem = kVariants[p->pb.variant].acc_f64 ? sizeof(double) : sizeof(float);
-    a.plane = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(plane) -
-                                       (uintptr_t)((size_t)p->t.tile_first[(size_t)dt] * (size_t)ld_plane * elem));
-    a.ld_plane = ld_plane;
-    return dispatch(p, a, true, pu::as_stream(stream));
-}
-
-}  // extern "C"

@@ -1,4 +1,5 @@
-// Internal helpers of exact.hip used by the search's certification step (dedisperse.hip).
+// Internal helpers of exact.hip used by the search's certification step
+// (dedisp_finalize.hip, dedisp_host.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,8 +1,8 @@
 // The dedispersion planner of libpulsarutils_hip: host arithmetic from (problem, shifts,
-// options) to the launch geometry and the tables the kernels of dedisperse.hip and
-// dedisp_f64.hip read.  Compiled by g++ (not hipcc), like planner.cpp:
-// no HIP header is in reach, so nothing here can touch a device.  -ffp-contract=off: the
-// cost model compares float64 sums.
+// options) to the launch geometry and the tables the kernels of dedisperse.hip,
+// dedisp_chan.hip and dedisp_f64.hip read.  Compiled by g++ (not hipcc),
+// like planner.cpp: no HIP header is in reach, so nothing here can touch a device.
+// -ffp-contract=off: the cost model compares float64 sums.
 #include <algorithm>
 #include <climits>
 #include <cmath>

@@ -307,6 +307,40 @@ def test_search_ragged_small(gpu, dt, group):
         np.testing.assert_array_equal(g[3], o[3])
 
 
+@pytest.mark.parametrize("dt,acc", [("u8", "native"), ("f32", "native"), ("u8", "f64"), ("f64", "f32")])
+def test_channel_kernel_group1_ragged(gpu, dt, acc):
+    """Every input / accumulator pair of dedisp_kernel (group 1, float32 rows), pinned by
+    plan.info: search and plane on the ragged shapes of test_search_ragged_small - a series
+    shorter than a time tile (wrapping DMA rows), partial last tiles, full tiles of both
+    tile lengths (256 and 512 samples) and several LDS chunks (the two-buffer ring).  The
+    oracle's best S/N beats the runner-up width by >= 1.18e-3 relative in every trial here,
+    a hundred times the float32 tolerance, so the widths are compared exactly."""
+    rng = np.random.default_rng(3)
+    exact = dt == "u8"  # the plane: integer sums below 2^24 are exact in float32 and float64
+    for nchan, n in [(3, 37), (5, 200), (31, 1001), (130, 3000)]:
+        x = (rng.random((nchan, n)) * 10).astype({"u8": np.uint8, "f32": np.float32, "f64": np.float64}[dt])
+        dms = np.linspace(0, 300, 23)
+        with D.planner_options(group=1):
+            g, plan = D.search_device(x, dms, nchan, 400., 100., 1e-3, acc=acc)
+        assert plan.info["kernel"] == 0 and plan.info["group"] == 1, plan.info
+        o = oracle.search(x, dms, 400., 100., 1e-3)
+        for a, b in zip(g[:3], o[:3]):
+            if acc == "f64":  # float64 statistics of an exact series
+                np.testing.assert_allclose(a.cpu().numpy(), b, rtol=1e-9)
+            else:  # float32 accumulation: the series (float input) and the tile statistics
+                np.testing.assert_allclose(a.cpu().numpy(), b, rtol=1e-5, atol=1e-9)
+        np.testing.assert_array_equal(g[3].cpu().numpy(), o[3])
+        plane = plan.dedisperse(_hip.to_device(x)).cpu().numpy()
+        sh = _hip.shift_table(nchan, dms, 400., 100., 1e-3)
+        assert plane.shape == (dms.size, n) and plane.dtype == (np.float64 if acc == "f64" else np.float32)
+        for k in range(dms.size):
+            ref = oracle.dedisperse(x, sh[k])
+            if exact:
+                np.testing.assert_array_equal(plane[k].astype(np.float64), ref)
+            else:
+                assert np.all(np.abs(plane[k] - ref) <= f32_bound(x, sh[k])), (nchan, n, k)
+
+
 @pytest.mark.parametrize("name", ["C2", "C5"])
 def test_search_full_size_all_trials(gpu, golden, name):
     """Full-size configs on device data; EVERY trial of the grid re-done by the C oracle
