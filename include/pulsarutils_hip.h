@@ -169,7 +169,8 @@ int pu_plan_exact_series(pu_plan *plan, const void *data, int64_t ld, const int3
                          int64_t t_begin, int64_t t_end, double *out, void *stream);
 
 /* *flag (device int32) = 1 if any of the nrows x ncols float32 / float64 elements (row
- * stride ld) is NaN or +-inf, else 0 (always 0 for uint8).  Asynchronous on stream. */
+ * stride ld) is NaN or +-inf, else 0 (always 0 for uint8, and for nrows == 0 or ncols == 0,
+ * when data may be NULL).  Asynchronous on stream. */
 int pu_nonfinite_any(const void *data, int dtype, int64_t nrows, int64_t ncols, int64_t ld, int32_t *flag,
                      void *stream);
 

@@ -361,13 +361,14 @@ int pu_plan_exact_series(pu_plan *p, const void *data, int64_t ld, const int32_t
 
 int pu_nonfinite_any(const void *data, int dtype, int64_t nrows, int64_t ncols, int64_t ld, int32_t *flag, void *stream)
 {
-    PU_REQUIRE(data && flag, "pu_nonfinite_any: NULL pointer");
+    PU_REQUIRE(flag, "pu_nonfinite_any: NULL pointer");
     PU_REQUIRE(nrows >= 0 && ncols >= 0 && ld >= ncols, "pu_nonfinite_any: bad shape");
     hipStream_t s = pu::as_stream(stream);
-    if (nrows == 0 || ncols == 0) {
+    if (nrows == 0 || ncols == 0) {  // nothing to read: data may be NULL (an empty torch view's pointer is)
         PU_TRY_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
         return PU_OK;
     }
+    PU_REQUIRE(data, "pu_nonfinite_any: NULL pointer");
     return pu::nonfinite_any_async(data, dtype, nrows, ncols, ld, flag, s);
 }
 

@@ -17,6 +17,7 @@ exactly (float64 channel-order series + numpy-order statistics), so:
 Goldens: tests/golden/make_golden.py ("degenerate" section); inputs rebuilt by
 tests/degenerate_cases.py and pinned by SHA-256.
 """
+import ctypes
 import hashlib
 
 import numpy as np
@@ -102,21 +103,28 @@ def test_degenerate_trials_c2_shape(gpu, golden, case):
     _check(case, np.empty(0, np.float32), got, ref, plan, None)
 
 
+def _series_rows(rng, n):
+    """The row kinds of a length: random, tied, constant, zero, NaN, inf, all negative."""
+    rows = []
+    rows.append(rng.standard_normal(n) * 3 + 7)
+    rows.append(np.repeat(rng.integers(0, 9, -(-n // 8)), 8)[:n].astype(np.float64))  # ties
+    rows.append(np.full(n, 0.1))
+    rows.append(np.zeros(n))
+    r = rng.standard_normal(n)
+    r[n // 2] = np.nan
+    rows.append(r)
+    r = rng.standard_normal(n)
+    r[0] = np.inf
+    rows.append(r)
+    rows.append(-np.abs(rng.standard_normal(n)) - 1.0)
+    return rows
+
+
 def _series_cases():
     rng = np.random.default_rng(8)
     rows = []
     for n in (8, 9, 100, 128, 129, 8192, 8193, 20000, (1 << 16) + 5):
-        rows.append(rng.standard_normal(n) * 3 + 7)
-        rows.append(np.repeat(rng.integers(0, 9, -(-n // 8)), 8)[:n].astype(np.float64))  # ties
-        rows.append(np.full(n, 0.1))
-        rows.append(np.zeros(n))
-        r = rng.standard_normal(n)
-        r[n // 2] = np.nan
-        rows.append(r)
-        r = rng.standard_normal(n)
-        r[0] = np.inf
-        rows.append(r)
-        rows.append(-np.abs(rng.standard_normal(n)) - 1.0)
+        rows += _series_rows(rng, n)
     return rows
 
 
@@ -137,6 +145,100 @@ def test_series_stats_bitexact_vs_oracle(gpu):
             want = oracle.trial_stats(r)
             np.testing.assert_array_equal(np.array([g[i] for g in got[:3]]), np.array(want[:3]), err_msg=f"n={n} row {i}")
             assert got[3][i] == want[3], (n, i, got[3][i], want[3])
+
+
+SENTINEL = -777.0
+
+
+def _raw_series_stats(series, index=None, workspace_bytes=None):
+    """pu_series_stats called directly: (return code, the four output arrays, pre-filled with
+    SENTINEL).  ``index``: int32 labels on the device or None; ``workspace_bytes``: the size
+    passed (default: what one batch of all the rows needs)."""
+    import torch
+    lib = _hip.lib()
+    rows, n = series.shape
+    wsb = lib.pu_series_stats_workspace_bytes(rows, n) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(wsb + 256, dtype=torch.uint8, device=series.device)
+    off = (-ws.data_ptr()) % 256
+    out = [torch.full((rows,), SENTINEL, dtype=torch.float64, device=series.device) for _ in range(3)]
+    out.append(torch.full((rows,), int(SENTINEL), dtype=torch.int32, device=series.device))
+    rc = lib.pu_series_stats(_hip.ptr(series), rows, n, series.stride(0), _hip.ptr(index), _hip.ptr(out[0]),
+                             _hip.ptr(out[1]), _hip.ptr(out[2]), _hip.ptr(out[3]), ctypes.c_void_p(ws.data_ptr() + off),
+                             wsb, _hip.stream_ptr())
+    return rc, [o.cpu().numpy() for o in out]
+
+
+def _padded_series(gpu, rows, pad=5):
+    """The rows as a view of a wider device tensor whose padding is NaN (ld = n + pad)."""
+    import torch
+    a = np.stack(rows)
+    wide = torch.full((a.shape[0], a.shape[1] + pad), float("nan"), dtype=torch.float64, device=gpu)
+    wide[:, :a.shape[1]] = torch.from_numpy(a).to(gpu)
+    return wide[:, :a.shape[1]]
+
+
+def _assert_stats(got, rows, where, index=None):
+    """Row r's outputs, at position index[r] (or r), equal oracle.trial_stats bit for bit."""
+    for r, row in enumerate(rows):
+        o = r if index is None else int(index[r])
+        want = oracle.trial_stats(row)
+        np.testing.assert_array_equal(np.array([g[o] for g in got[:3]]), np.array(want[:3]),
+                                      err_msg=f"{where} row {r} at {o}")
+        assert got[3][o] == want[3], (where, r, o, got[3][o], want[3])
+
+
+# the lengths at which the rebinned lengths n // 2, n // 4, n // 8 cross 8, 128 and 8192 (numpy's
+# pairwise-sum unroll, tail and block sizes), and every length from 8 to 17 (n // 8 = 1 and 2)
+@pytest.mark.parametrize("n", list(range(8, 18)) + [24, 127, 1023, 1025, 8191, 8200])
+def test_series_stats_c_abi_padding_and_index(gpu, n):
+    """pu_series_stats through the C ABI on rows of a padded tensor (ld = n + 5, the padding NaN:
+    a read past a row's n samples poisons its statistics) without and with an index that is a
+    permutation of the rows: row r's outputs land at index[r], every slot of the pre-filled
+    outputs is written, and every value equals oracle.trial_stats bit for bit."""
+    import torch
+    rng = np.random.default_rng(800 + n)
+    rows = _series_rows(rng, n)
+    series = _padded_series(gpu, rows)
+    assert series.stride(0) == n + 5
+    rc, got = _raw_series_stats(series)
+    assert rc == 0, _hip.lib().pu_last_error()
+    _assert_stats(got, rows, f"n={n}")
+    perm = rng.permutation(len(rows)).astype(np.int32)
+    assert not np.array_equal(perm, np.arange(len(rows)))
+    rc, got = _raw_series_stats(series, index=torch.from_numpy(perm).to(gpu))
+    assert rc == 0, _hip.lib().pu_last_error()
+    _assert_stats(got, rows, f"n={n} indexed", perm)
+    # a permutation: each slot is some row's, and each was compared above; none kept the fill
+    assert sorted(perm.tolist()) == list(range(len(rows)))
+    assert not any((g == SENTINEL).any() for g in got)
+
+
+def test_series_stats_c_abi_batches(gpu):
+    """7 rows with a workspace of exactly pu_series_stats_workspace_bytes(2, n): the call halves
+    its batch 7 -> 4 -> 2 and runs batches of 2, 2, 2 and 1 rows (4 rows do not fit, asserted).
+    The results equal the one-batch call's and the oracle's, without and with an index (whose
+    batches offset the index, not the outputs); a workspace that holds no row is PU_EINVAL
+    before any launch."""
+    import torch
+    n = 1025
+    rng = np.random.default_rng(77)
+    rows = _series_rows(rng, n)
+    assert len(rows) == 7
+    series = _padded_series(gpu, rows)
+    size = _hip.lib().pu_series_stats_workspace_bytes
+    two = size(2, n)
+    assert size(1, n) < two < size(4, n)
+    perm = torch.from_numpy(np.array([4, 0, 6, 2, 5, 1, 3], np.int32)).to(gpu)
+    for index in (None, perm):
+        rc1, one = _raw_series_stats(series, index=index)
+        rcb, batched = _raw_series_stats(series, index=index, workspace_bytes=two)
+        assert rc1 == 0 and rcb == 0, _hip.lib().pu_last_error()
+        for a, b in zip(one, batched):
+            np.testing.assert_array_equal(a, b)
+        _assert_stats(batched, rows, "batched", None if index is None else perm.cpu().numpy())
+    rc, untouched = _raw_series_stats(series, workspace_bytes=size(1, n) - 256)
+    assert rc == _hip._EINVAL
+    assert all((g == SENTINEL).all() for g in untouched)
 
 
 def test_nearconst_f32_c2_shape_vs_oracle(gpu):

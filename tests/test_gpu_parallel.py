@@ -3,6 +3,8 @@ under a world-size-1 RCCL (nccl) process group, and the pipelined broadcast + se
 (time-tile range launches, pu_plan_search_tiles + pu_plan_finalize) against the one-shot
 search.  The multi-rank split / broadcast / gather plumbing is covered on CPU by
 tests/test_parallel_gloo.py (gloo, world 2-4)."""
+import ctypes
+import functools
 import socket
 
 import numpy as np
@@ -251,7 +253,10 @@ def test_exact_series_ranges_equal_oracle_rows(gpu, dt):
     """pu_plan_exact_series (the certification recompute; loads of 8/4/2 channels issued ahead
     of their adds, round 6) equals the oracle's float64 channel-order rows bit for bit, over
     the whole series and over sample ranges that start and end anywhere (ragged n, windows
-    wrapping modulo n)."""
+    wrapping modulo n).  For u8 this length covers the element-by-element path of the generic
+    kernel only: n = 70001 gives ld % 4 != 0, so pu::exact_series skips
+    exact_series_u8_seg_kernel and the generic kernel's dword path is off too (rows4 false);
+    the 8-bit production kernels are test_exact_series_u8_* below."""
     import torch
     n, nchan = 70001, 37
     rng = np.random.default_rng(7)
@@ -266,3 +271,163 @@ def test_exact_series_ranges_equal_oracle_rows(gpu, dt):
     np.testing.assert_array_equal(plan.exact_series(xd, tr).cpu().numpy(), want)
     for a, b in [(0, 1), (5, 4100), (n - 700, n), (12345, 12346 + 8 * 513)]:
         np.testing.assert_array_equal(plan.exact_series(xd, tr, t_begin=a, t_end=b).cpu().numpy(), want[:, a:b])
+
+
+# ------------------------------------------------------------------ exact series: production kernels
+
+SEG_NCHAN, SEG_N = 300, 70000   # two 256-channel segments; the second 44 = 5 x 8 + 4 channels
+SEG_RANGES = [(0, 1), (5, 4100), (SEG_N - 700, SEG_N), (12345, 12346 + 8 * 513), (3, 3 + 8 * 64 + 5)]
+
+
+def _series_input(dt, nchan, n):
+    rng = np.random.default_rng(7)
+    return {"u8": lambda: rng.integers(0, 256, (nchan, n)).astype(np.uint8),
+            "f32": lambda: rng.random((nchan, n)).astype(np.float32), "f64": lambda: rng.random((nchan, n))}[dt]()
+
+
+@functools.lru_cache(maxsize=None)
+def _series_case(dt, nchan, n):
+    """(input, shift table, the oracle's rows of every trial), computed once and read-only."""
+    x = _series_input(dt, nchan, n)
+    sh = _hip.shift_table(nchan, np.linspace(0.0, 400.0, 9), 1200.0, 300.0, 64e-6)
+    want = np.stack([oracle.dedisperse(x, sh[d]) for d in range(sh.shape[0])])
+    for a in (x, sh, want):
+        a.setflags(write=False)
+    return x, sh, want
+
+
+def _raw_exact_series(plan, data, a, b):
+    """pu_plan_exact_series of every trial on the tensor as it is (no aligning copy)."""
+    import torch
+    tr = np.arange(plan.ndm, dtype=np.int32)
+    out = torch.full((tr.size, b - a), -1.0, dtype=torch.float64, device=data.device)
+    _hip.check(_hip.lib().pu_plan_exact_series(plan._h, _hip.ptr(data), data.stride(0),
+                                               tr.ctypes.data_as(ctypes.c_void_p), tr.size, a, b, _hip.ptr(out),
+                                               _hip.stream_ptr()), "pu_plan_exact_series")
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("dt", ["u8", "f32", "f64"])
+def test_exact_series_channel_segments_equal_oracle_rows(gpu, dt):
+    """nchan = 300, n = 70000 (ld % 4 == 0): 8-bit input runs exact_series_u8_seg_kernel, what
+    every aligned 8-bit tensor gets - two channel segments, the second partial (unrolled
+    groups of 8 and a four-channel tail), integer sums added by float64 atomics, the
+    three-dword funnel-shift reads; float input the generic kernel over more than one
+    unrolled group.  Whole series and ranges that start and end anywhere, ranges shorter than
+    a thread's 8 samples and ending inside a wave's 512 included: bit-equal to the oracle."""
+    import torch
+    x, sh, want = _series_case(dt, SEG_NCHAN, SEG_N)
+    xd = torch.from_numpy(x.copy()).cuda()
+    assert xd.stride(0) % 4 == 0 and xd.data_ptr() % 4 == 0
+    plan = _hip.Plan(_hip.dtype_code(xd.dtype), _hip.PU_ACC_F64, SEG_NCHAN, SEG_N, sh)
+    tr = np.arange(sh.shape[0], dtype=np.int32)
+    np.testing.assert_array_equal(plan.exact_series(xd, tr).cpu().numpy(), want)
+    for a, b in SEG_RANGES:
+        np.testing.assert_array_equal(plan.exact_series(xd, tr, t_begin=a, t_end=b).cpu().numpy(), want[:, a:b],
+                                      err_msg=f"samples [{a}, {b})")
+
+
+@pytest.mark.parametrize("off,pad", [(0, 4), (4, 0), (0, 3), (3, 0)])
+def test_exact_series_u8_padded_rows(gpu, off, pad):
+    """The same 8-bit data as a view of a wider tensor filled with 255.  Row stride n + 4 with
+    the rows on 4-byte boundaries: the segment kernel with ld != n.  Row stride n + 3 (through
+    the C call, on a plan that does not stage rows by LDS-DMA: the wrapper would copy such a
+    view): the generic kernel, element by element.  A row pointer computed with n for ld, or a
+    read past a row's n samples, adds a wrong byte to an integer sum."""
+    import torch
+    x, sh, want = _series_case("u8", SEG_NCHAN, SEG_N)
+    big = torch.full((SEG_NCHAN, off + SEG_N + pad), 255, dtype=torch.uint8, device=gpu)
+    view = big[:, off:off + SEG_N]
+    view.copy_(torch.from_numpy(x.copy()))
+    plan = _hip.Plan(_hip.PU_U8, _hip.PU_ACC_F64, SEG_NCHAN, SEG_N, sh, u8_dma=False)
+    aligned = (off + pad) % 4 == 0
+    assert view.stride(0) == SEG_N + off + pad and (view.data_ptr() % 4 == 0 and view.stride(0) % 4 == 0) == aligned
+    if aligned:  # the wrapper passes the view itself
+        assert plan._rows_aligned(view) is view
+        tr = np.arange(sh.shape[0], dtype=np.int32)
+        np.testing.assert_array_equal(plan.exact_series(view, tr).cpu().numpy(), want)
+    np.testing.assert_array_equal(_raw_exact_series(plan, view, 0, SEG_N), want)
+    for a, b in SEG_RANGES:
+        np.testing.assert_array_equal(_raw_exact_series(plan, view, a, b), want[:, a:b], err_msg=f"samples [{a}, {b})")
+
+
+@pytest.mark.parametrize("dt", ["u8", "f32", "f64"])
+def test_exact_series_shorter_than_a_wave(gpu, dt):
+    """nchan = 9, n = 40: the series is shorter than the 512 samples a wave owns, so a thread's
+    window wraps modulo n more than once (8-bit: the segment kernel, ld = 40; one unrolled
+    group of 8 channels and a tail of one)."""
+    import torch
+    nchan, n = 9, 40
+    x, sh, want = _series_case(dt, nchan, n)
+    assert sh.max() >= n  # shifts beyond the series: reduced modulo n
+    xd = torch.from_numpy(x.copy()).cuda()
+    plan = _hip.Plan(_hip.dtype_code(xd.dtype), _hip.PU_ACC_F64, nchan, n, sh)
+    tr = np.arange(sh.shape[0], dtype=np.int32)
+    np.testing.assert_array_equal(plan.exact_series(xd, tr).cpu().numpy(), want)
+    np.testing.assert_array_equal(plan.exact_series(xd, tr, t_begin=7, t_end=33).cpu().numpy(), want[:, 7:33])
+
+
+# ------------------------------------------------------------------ pu_nonfinite_any
+
+def _flag_of(x, preset):
+    """pu_nonfinite_any's flag for x, the flag tensor holding ``preset`` before the call."""
+    import torch
+    flag = torch.full((1,), preset, dtype=torch.int32, device=x.device)
+    return int(_hip.nonfinite_any(x, flag)[0])
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (3, 1000), (17, 70001)])
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_nonfinite_any_every_corner(gpu, dt, shape):
+    """NaN, +inf and -inf at the first and last element of the first and last row each set the
+    flag; clean data and the finite extremes (largest, smallest subnormal, -0.0) clear a flag
+    left at 1.  (17, 70001) is more than 4096 x 256 elements: the grid-stride loop runs twice."""
+    import torch
+    tdt = {"f32": torch.float32, "f64": torch.float64}[dt]
+    rows, n = shape
+    rng = np.random.default_rng(rows * n)
+    x = torch.from_numpy(rng.standard_normal(shape)).to(tdt).to(gpu)
+    assert _flag_of(x, 1) == 0
+    for r, c in sorted({(0, 0), (0, n - 1), (rows - 1, 0), (rows - 1, n - 1)}):
+        keep = x[r, c].item()
+        for bad in (float("nan"), float("inf"), float("-inf")):
+            x[r, c] = bad
+            assert _flag_of(x, 0) == 1, (r, c, bad)
+        fi = torch.finfo(tdt)
+        for ok in (fi.max, -fi.max, fi.smallest_normal * fi.eps, -0.0):
+            x[r, c] = ok
+            assert x[r, c].item() == ok and _flag_of(x, 1) == 0, (r, c, ok)
+        x[r, c] = keep
+    assert _flag_of(x, 1) == 0
+
+
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_nonfinite_any_padding_uint8_and_empty(gpu, dt):
+    """Only the nrows x ncols elements count: NaN in the padding of a view (ld = n + 3) is not
+    seen, a NaN in the view's last column is.  A uint8 tensor and an empty one (no rows, or no
+    columns: the column range of a rank with no time tiles, whose torch pointer is NULL) give 0,
+    resetting a flag left at 1."""
+    import torch
+    tdt = {"f32": torch.float32, "f64": torch.float64}[dt]
+    rows, n = 5, 1001
+    big = torch.full((rows, n + 3), float("nan"), dtype=tdt, device=gpu)
+    view = big[:, :n]
+    view.fill_(1.5)
+    assert view.stride(0) == n + 3 and torch.isnan(big[:, n:]).all()
+    assert _flag_of(view, 1) == 0
+    for r in (0, 2, rows - 1):
+        big[r, n - 1] = float("nan")
+        assert _flag_of(view, 0) == 1, r
+        big[r, n - 1] = 1.5
+    assert _flag_of(view, 1) == 0
+    assert _flag_of(torch.full((7, 300), 255, dtype=torch.uint8, device=gpu), 1) == 0
+    big[1, 2] = float("inf")
+    assert _flag_of(view, 0) == 1
+    for empty in (view[:0], view[:, 2:2]):
+        assert empty.numel() == 0
+        assert _flag_of(empty, 1) == 0
+    # the C call itself with a real pointer and no rows
+    flag = torch.ones(1, dtype=torch.int32, device=gpu)
+    _hip.check(_hip.lib().pu_nonfinite_any(_hip.ptr(view), _hip.dtype_code(tdt), 0, n, n + 3, _hip.ptr(flag),
+                                           _hip.stream_ptr()), "pu_nonfinite_any")
+    assert int(flag[0]) == 0
