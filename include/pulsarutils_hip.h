@@ -588,6 +588,83 @@ int pu_profile_chi2(const double *sums, int64_t ld_trial, int64_t ld_row, const 
                     int64_t rows, int64_t ntrials, int64_t nbin, const double *mean, const double *var,
                     double *chi2, int32_t *dof, void *stream);
 
+/* ------------------------------------------------------------------ FFT periodicity search */
+
+/* Real-to-complex FFT of rows series: the first step of the blind periodicity search (no reference
+ * counterpart).  x: device, rows series of n samples, leading dimension ld (PU_F32 / PU_F64; PU_U8
+ * is PU_EUNSUPPORTED, as in pu_fold_trials).  mean: device float64 [rows], NULL means 0.  nfft: a
+ * power of two, 2^8 <= nfft <= 2^24, n <= nfft.  For row r
+ *     y[t] = (float)((double)x[r][t] - mean[r])   for t < n   (one float64 subtraction, one
+ *            rounding to float32)
+ *     y[t] = 0                                    for n <= t < nfft
+ *     spec[r * ld_spec + k] = sum_t y[t] e^(-2 pi i k t / nfft),   k = 0 .. nfft / 2
+ * as complex64 (float re, im), ld_spec >= nfft / 2 + 1 complex elements.  Arithmetic: float32,
+ * no fused multiply-add, twiddles e^(-2 pi i k / nfft) rounded to float32 from float64
+ * sincospi (a table at the start of the workspace, rebuilt by every call).  The half-length
+ * complex transform of z[j] = y[2j] + i y[2j+1] runs in one LDS pass (nfft <= 2^13) or two
+ * (four-step, nfft/2 = N1 x N2), radix-2 decimation in frequency, and a split step makes the
+ * real-input spectrum in place in spec.  The order of every operation is fixed by nfft alone:
+ * two equal calls give equal bits, and a row's bits depend neither on rows, on its position in
+ * the batch nor on ld.  Error: the Cooley-Tukey bound, ||spec - exact||_2 <= 8 log2(nfft) 2^-24
+ * ||exact||_2 per row (Higham, Accuracy and Stability of Numerical Algorithms, Thm 24.2).
+ * workspace: pu_rfft_workspace_bytes(rows, nfft) bytes, 256-byte aligned: the twiddle table
+ * (nfft / 2 complex64) and, above 2^13, rows x nfft / 2 complex64 between the two passes.
+ * PU_EUNSUPPORTED: dtype.  PU_EINVAL: nfft not a power of two in [2^8, 2^24]; n < 0, n > nfft,
+ * rows < 0 or > 65535; ld < n; ld_spec < nfft / 2 + 1; a NULL or misaligned pointer; a workspace too small
+ * or not 256-byte aligned.  PU_OK without a launch for rows == 0.  All checked before any HIP
+ * call; asynchronous on stream. */
+size_t pu_rfft_workspace_bytes(int64_t rows, int64_t nfft);
+int pu_rfft(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *mean, int64_t nfft,
+            void *spec, int64_t ld_spec, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Power spectrum with the red noise taken out by a running median in blocks.  spec: device
+ * complex64, rows x ld_spec (pu_rfft's output); nb = nfft / 2 bins k = 0 .. nb - 1 (the Nyquist
+ * bin is dropped); block B: a power of two, 16 <= B <= min(1024, nb).  In float32, every step
+ * one IEEE operation and no fused multiply-add:
+ *     P[k] = re * re + im * im
+ * Per block b (bins b B .. (b + 1) B - 1): s = the block's powers sorted ascending, with P[0]
+ * replaced by +inf in block 0;
+ *     med = 0.5f * (s[B/2 - 1] + s[B/2])      (block 0: med = s[B/2 - 1], the median of its
+ *                                              B - 1 real bins)
+ * If any power of the block is not finite (the replaced P[0] does not count) every output of
+ * the block is NaN; otherwise if !(med > 0) every output is 0; otherwise
+ *     out[r * ld_out + k] = P[k] * (0.6931472f / med)        (one division per block)
+ * and out[r * ld_out + 0] = 0 always.  Noise then has mean about 1, each bin about Exp(1).
+ * out: device float32, rows x ld_out, ld_out >= nb.  PU_EINVAL: nb not a power of two in [2^7,
+ * 2^23], a bad block, rows < 0 or > 65535, ld_spec < nb, ld_out < nb, NULL pointers.  PU_OK without a
+ * launch for rows == 0.  All checked before any HIP call; asynchronous on stream. */
+int pu_spectrum_normalize(const void *spec, int64_t rows, int64_t nb, int64_t ld_spec, int64_t block,
+                          float *out, int64_t ld_out, void *stream);
+
+/* Incoherent harmonic sums of normalised spectra and their significant local maxima.  norm:
+ * device float32, rows x ld (pu_spectrum_normalize's output), nb bins.  nlev levels, 1 <= nlev
+ * <= 6; level l sums H = 2^l harmonics.  For every k in 0 .. nb - 1, in float32:
+ *     S_0[k]     = norm[k]
+ *     S_(l+1)[k] = S_l[k] + sum over odd m = 1, 3, .. 2H - 1 of norm[(k m + H) / (2H)],  H = 2^l
+ * the terms added one at a time in ascending m to a running sum that starts at S_l[k]; the
+ * division is an int64 division.  k is the bin of the TOP harmonic: the fundamental is at k / 2^l
+ * bins.  sums (device, may be NULL: nothing is written): sums[l * ld_level + r * ld_row + k].
+ * Candidates: thr (float32), kmin, kmax (int64): HOST arrays of nlev entries.  Bin k with kmin[l]
+ * <= k < kmax[l] is a candidate of level l iff S_l[k] > thr[l], S_l[k] > S_l[k - 1] and S_l[k] >=
+ * S_l[k + 1]; a neighbour outside [0, nb) counts as -inf; NaN compares false.  Candidates are
+ * delivered sorted by (row, level, bin): *count (host) receives their number and the first
+ * min(*count, cap) are written to cands (device; may be NULL when cap == 0: the call then only
+ * counts).  Count, scan and fill kernels with integer arithmetic only: the order and the total
+ * do not depend on timing.  workspace: pu_harmonic_search_workspace_bytes(rows, nb, nlev),
+ * 256-byte aligned.  PU_EINVAL: nlev outside [1, 6], rows < 0 or > 65535, nb < 1 or > 2^23, ld <
+ * nb, bad strides of sums, cap < 0, NULL pointers, a workspace too small or misaligned.  All
+ * checked before any HIP call.  The call synchronises the stream once (as pu_series_events). */
+typedef struct pu_spec_cand {
+    int32_t row, level;
+    int64_t bin;
+    float power, pad;
+} pu_spec_cand;
+size_t pu_harmonic_search_workspace_bytes(int64_t rows, int64_t nb, int64_t nlev);
+int pu_harmonic_search(const float *norm, int64_t rows, int64_t nb, int64_t ld, int64_t nlev, float *sums,
+                       int64_t ld_level, int64_t ld_row, const float *thr, const int64_t *kmin,
+                       const int64_t *kmax, pu_spec_cand *cands, int64_t cap, int64_t *count,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,305 @@
+// Real-to-complex FFT of dedispersed series for gfx950: pu_rfft (include/pulsarutils_hip.h).
+//
+// A row of nfft real samples is packed as M = nfft / 2 complex ones, z[j] = y[2j] + i y[2j+1]; the
+// complex transform Z of length M runs in LDS and a split step turns Z into the real-input
+// spectrum.  The mean subtraction, the float64 -> float32 rounding and the zero padding happen
+// where the first pass loads its samples.
+//
+//   M <= 4096 (nfft <= 2^13): one pass.  A workgroup loads the row, transforms it, and writes Z in
+//       natural order into the output row.
+//   above: four-step, M = N1 x N2 with N1 = 2^floor(log2 M / 2) <= N2 <= 4096, j = j1 N2 + j2,
+//       k = k1 + N1 k2:
+//         pass 1 (rfft_cols_kernel): a workgroup owns C = 8192 / N1 consecutive columns j2, laid
+//           out in LDS [j1][c] (c fastest: a butterfly's lanes are contiguous, no bank conflict
+//           while C h >= 32); transforms over j1, multiplies by W_M^(j2 k1) and writes
+//           T[k1][j2] to the workspace (segments of C x 8 bytes);
+//         pass 2 (rfft_rows_kernel): a workgroup owns R = 8192 / N2 consecutive rows k1 of T, laid
+//           out [r][N2 + 1] (the odd pitch spreads the transposing read-out over the banks);
+//           transforms over j2 and writes Z[k1 + N1 k2] into the output row (segments of R x 8
+//           bytes).
+//   split (rfft_split_kernel), in place in the output row: thread j <= M / 2 reads Z[j] and
+//       Z[M - j] and writes X[j] and X[M - j];  X[k] = E + W^k O with E = (Z[k] + conj Z[M-k]) / 2,
+//       O = -i (Z[k] - conj Z[M-k]) / 2, W = e^(-2 pi i / nfft), Z[M] = Z[0].
+//
+// The LDS transform is radix-2 decimation in frequency, in place, natural order in and
+// bit-reversed order out (the write-out undoes it): log2 N stages with a barrier each.  Stage
+// twiddles come from an LDS copy of W_N^j (j < N / 2), itself read from the table W_nfft^k
+// (k < nfft / 2) that rfft_twiddle_kernel makes at the start of the workspace with float64
+// sincospi rounded once to float32.  No fused multiply-add (-ffp-contract=off), no atomics, and
+// every operation's order is fixed by nfft: a row's bits depend on nothing but its samples.
+//
+// LDS per workgroup: 8192 complex64 of data (64 KiB, + R pads) + N / 2 twiddles (<= 16 KiB):
+// at most 82 KiB of the CU's 160 KiB.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "pu_common.h"
+
+namespace {
+
+constexpr int RF_TILE = 8192;    // complex elements of a workgroup's LDS tile
+constexpr int RF_THREADS = 512;  // 8 waves
+constexpr int RF_MAX_LOG = 12;   // longest LDS transform: 4096
+
+struct RfShape {
+    int lm, l1, l2;  // log2 of M, N1, N2 (l1 = 0: one pass)
+    int lc, lr;      // log2 of the columns (pass 1) / rows (pass 2) of a workgroup
+};
+
+RfShape rf_shape(int64_t nfft)
+{
+    RfShape s{};
+    int lg = 0;
+    while (((int64_t)1 << lg) < nfft) ++lg;
+    s.lm = lg - 1;
+    if (s.lm <= RF_MAX_LOG) {
+        s.l1 = 0, s.l2 = s.lm, s.lc = 0, s.lr = 0;
+    } else {
+        s.l1 = s.lm / 2, s.l2 = s.lm - s.l1;
+        s.lc = 13 - s.l1, s.lr = 13 - s.l2;
+    }
+    return s;
+}
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 w)
+{
+    return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
+}
+
+// tbl[k] = e^(-2 pi i k / nfft), k < nfft / 2: float64 sincospi, rounded once
+__global__ void rfft_twiddle_kernel(float2 *__restrict__ tbl, int64_t nfft)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nfft / 2) return;
+    double sn, cs;
+    sincospi(2.0 * (double)k / (double)nfft, &sn, &cs);  // 2 k / nfft is exact
+    tbl[k] = make_float2((float)cs, (float)-sn);
+}
+
+// W_nfft^e for 0 <= e < nfft from the half table
+__device__ __forceinline__ float2 rf_tw(const float2 *__restrict__ tbl, int e, int half)
+{
+    if (e < half) return tbl[e];
+    const float2 w = tbl[e - half];
+    return make_float2(-w.x, -w.y);
+}
+
+// In-place radix-2 DIF of 2^lv vectors of 2^ln elements in LDS.  COLS: element i of vector c at
+// s[(i << lv) + c]; otherwise at s[c * ((1 << ln) + 1) + i].  tw[j] = W_N^j, j < N / 2.
+template <bool COLS>
+__device__ __forceinline__ void rf_lds_fft(float2 *s, const float2 *tw, int ln, int lv)
+{
+    const int half = 1 << (ln - 1), work = half << lv, pitch = (1 << ln) + 1;
+    for (int st = 0; st < ln; ++st) {
+        const int lh = ln - 1 - st, h = 1 << lh;
+        __syncthreads();
+        for (int w = threadIdx.x; w < work; w += blockDim.x) {
+            const int c = COLS ? w & ((1 << lv) - 1) : w >> (ln - 1);
+            const int b = COLS ? w >> lv : w & (half - 1);
+            const int p = b & (h - 1), i0 = ((b >> lh) << (lh + 1)) + p, i1 = i0 + h;
+            const int a0 = COLS ? (i0 << lv) + c : c * pitch + i0;
+            const int a1 = COLS ? (i1 << lv) + c : c * pitch + i1;
+            const float2 u = s[a0], v = s[a1];
+            s[a0] = make_float2(u.x + v.x, u.y + v.y);
+            s[a1] = cmul(make_float2(u.x - v.x, u.y - v.y), tw[p << st]);
+        }
+    }
+    __syncthreads();
+}
+
+// z[j] of a row: the packed, mean-subtracted, float32-rounded, zero-padded samples 2j, 2j + 1
+template <typename T>
+__device__ __forceinline__ float2 rf_sample(const T *__restrict__ row, int64_t n, double mu, int64_t j)
+{
+    const int64_t t = 2 * j;
+    const float a = t < n ? (float)((double)row[t] - mu) : 0.0f;
+    const float b = t + 1 < n ? (float)((double)row[t + 1] - mu) : 0.0f;
+    return make_float2(a, b);
+}
+
+__device__ __forceinline__ int rf_brev(int i, int ln) { return (int)(__brev((unsigned)i) >> (32 - ln)); }
+
+// pass 1 of the four-step: columns j2 of z (N1 x N2) -> T[k1][j2] W_M^(j2 k1)
+template <typename T>
+__global__ void __launch_bounds__(RF_THREADS)
+rfft_cols_kernel(const T *__restrict__ x, int64_t n, int64_t ld, const double *__restrict__ mean, RfShape sh,
+                 const float2 *__restrict__ tbl, float2 *__restrict__ tws)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
+    float2 *s = reinterpret_cast<float2 *>(rf_smem);  // [N1][C]
+    float2 *tw = s + RF_TILE;                          // [N1 / 2]
+    const int n1 = 1 << sh.l1, n2 = 1 << sh.l2, cmask = (1 << sh.lc) - 1, half = 1 << sh.lm;
+    const int groups = n2 >> sh.lc;
+    const int64_t r = blockIdx.x / groups;
+    const int j20 = (int)(blockIdx.x % groups) << sh.lc;
+    const T *row = x + r * ld;
+    const double mu = mean ? mean[r] : 0.0;
+    for (int j = threadIdx.x; j < n1 / 2; j += blockDim.x) tw[j] = tbl[(int64_t)j << (sh.lm + 1 - sh.l1)];
+    for (int w = threadIdx.x; w < RF_TILE; w += blockDim.x) {
+        const int c = w & cmask, j1 = w >> sh.lc;
+        s[w] = rf_sample(row, n, mu, (int64_t)j1 * n2 + j20 + c);
+    }
+    rf_lds_fft<true>(s, tw, sh.l1, sh.lc);
+    float2 *dst = tws + r * (int64_t)half;
+    for (int w = threadIdx.x; w < RF_TILE; w += blockDim.x) {
+        const int c = w & cmask, k1 = rf_brev(w >> sh.lc, sh.l1), j2 = j20 + c;
+        dst[(int64_t)k1 * n2 + j2] = cmul(s[w], rf_tw(tbl, 2 * j2 * k1, half));  // 2 j2 k1 < nfft <= 2^24
+    }
+}
+
+// pass 2 of the four-step (rows k1 of T -> Z[k1 + N1 k2]), or the whole transform of a short row
+// (FROM_X: N1 = 1, one row of z per workgroup)
+template <typename T, bool FROM_X>
+__global__ void __launch_bounds__(RF_THREADS)
+rfft_rows_kernel(const T *__restrict__ x, int64_t n, int64_t ld, const double *__restrict__ mean, RfShape sh,
+                 const float2 *__restrict__ tbl, const float2 *__restrict__ tws, float2 *__restrict__ spec,
+                 int64_t ld_spec)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
+    const int n1 = 1 << sh.l1, n2 = 1 << sh.l2, pitch = n2 + 1, nr = 1 << sh.lr, half = 1 << sh.lm;
+    float2 *s = reinterpret_cast<float2 *>(rf_smem);  // [R][N2 + 1]
+    float2 *tw = s + nr * pitch;                       // [N2 / 2]
+    const int groups = n1 >> sh.lr;
+    const int64_t r = blockIdx.x / groups;
+    const int k10 = (int)(blockIdx.x % groups) << sh.lr;
+    for (int j = threadIdx.x; j < n2 / 2; j += blockDim.x) tw[j] = tbl[(int64_t)j << (sh.lm + 1 - sh.l2)];
+    const int total = nr << sh.l2;
+    if (FROM_X) {
+        const T *row = x + r * ld;
+        const double mu = mean ? mean[r] : 0.0;
+        for (int w = threadIdx.x; w < total; w += blockDim.x) s[w] = rf_sample(row, n, mu, w);
+    } else {
+        const float2 *src = tws + r * (int64_t)half + (int64_t)k10 * n2;
+        for (int w = threadIdx.x; w < total; w += blockDim.x) s[(w >> sh.l2) * pitch + (w & (n2 - 1))] = src[w];
+    }
+    rf_lds_fft<false>(s, tw, sh.l2, sh.lr);
+    float2 *dst = spec + r * ld_spec;
+    for (int w = threadIdx.x; w < total; w += blockDim.x) {
+        const int rr = w & (nr - 1), i = w >> sh.lr;
+        dst[k10 + rr + (int64_t)n1 * rf_brev(i, sh.l2)] = s[rr * pitch + i];
+    }
+}
+
+// Z (M values at the start of each output row) -> the nfft / 2 + 1 bins of the real transform
+__global__ void __launch_bounds__(256)
+rfft_split_kernel(float2 *__restrict__ spec, int64_t ld_spec, int64_t m, const float2 *__restrict__ tbl)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > m / 2) return;
+    float2 *row = spec + (int64_t)blockIdx.y * ld_spec;
+    const float2 za = row[j], zb = row[j ? m - j : 0];
+    // bin j: Zk = za, Zm = conj(zb); bin m - j: Zk = zb, Zm = conj(za)
+    const float2 ea = make_float2(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));
+    const float2 oa = make_float2(0.5f * (za.y + zb.y), -0.5f * (za.x - zb.x));
+    if (j == 0) {
+        row[0] = make_float2(ea.x + oa.x, ea.y + oa.y);
+        row[m] = make_float2(ea.x - oa.x, ea.y - oa.y);
+        return;
+    }
+    const float2 wa = tbl[j], pa = cmul(oa, wa);
+    const float2 xa = make_float2(ea.x + pa.x, ea.y + pa.y);
+    if (2 * j == m) {
+        row[j] = xa;
+        return;
+    }
+    // W^(m - j) = -conj(W^j)
+    const float2 eb = make_float2(ea.x, -ea.y);
+    const float2 ob = make_float2(oa.x, -oa.y);
+    const float2 pb = cmul(ob, make_float2(-wa.x, wa.y));
+    row[j] = xa;
+    row[m - j] = make_float2(eb.x + pb.x, eb.y + pb.y);
+}
+
+bool rf_valid_nfft(int64_t nfft) { return nfft >= 256 && nfft <= ((int64_t)1 << 24) && (nfft & (nfft - 1)) == 0; }
+
+size_t rf_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+size_t pu_rfft_workspace_bytes(int64_t rows, int64_t nfft)
+{
+    if (rows <= 0 || !rf_valid_nfft(nfft)) return 0;
+    const RfShape sh = rf_shape(nfft);
+    const size_t tbl = rf_up256((size_t)(nfft / 2) * sizeof(float2));
+    if (sh.l1 == 0) return tbl;
+    if ((size_t)rows > (SIZE_MAX - tbl) / ((size_t)(nfft / 2) * sizeof(float2))) return SIZE_MAX;
+    return tbl + (size_t)rows * (size_t)(nfft / 2) * sizeof(float2);
+}
+
+int pu_rfft(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *mean, int64_t nfft, void *spec,
+            int64_t ld_spec, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (dtype != PU_F32 && dtype != PU_F64) {
+        pu::set_error("pu_rfft: unsupported dtype %d (a dedispersed series is float32 or float64)", dtype);
+        return PU_EUNSUPPORTED;
+    }
+    PU_REQUIRE(rf_valid_nfft(nfft), "pu_rfft: nfft %lld is not a power of two in [2^8, 2^24]", (long long)nfft);
+    PU_REQUIRE(rows >= 0 && n >= 0 && n <= nfft, "pu_rfft: bad size (rows %lld, n %lld, nfft %lld)", (long long)rows,
+               (long long)n, (long long)nfft);
+    PU_REQUIRE(ld >= n && ld_spec >= nfft / 2 + 1, "pu_rfft: leading dimension too small (ld %lld < n %lld or ld_spec "
+               "%lld < nfft / 2 + 1)", (long long)ld, (long long)n, (long long)ld_spec);
+    if (rows == 0) return PU_OK;
+    const RfShape sh = rf_shape(nfft);
+    const int64_t m = nfft / 2;
+    const int64_t groups = sh.l1 ? ((int64_t)1 << (sh.l1 - sh.lr)) : 1, cgroups = sh.l1 ? ((int64_t)1 << (sh.l2 - sh.lc)) : 1;
+    PU_REQUIRE(rows <= 65535 && rows <= INT32_MAX / groups && rows <= INT32_MAX / cgroups,
+               "pu_rfft: %lld rows exceed the grid limit (65535 per call)", (long long)rows);
+    const size_t need = pu_rfft_workspace_bytes(rows, nfft);
+    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
+               "pu_rfft: workspace of %zu bytes (256-byte aligned) needed, got %zu", need, workspace_bytes);
+    PU_REQUIRE(x && spec, "pu_rfft: null pointer");
+    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % pu::elem_size(dtype) == 0 && reinterpret_cast<uintptr_t>(spec) % 8 == 0,
+               "pu_rfft: x or spec is not aligned to its element type");
+    hipStream_t s = pu::as_stream(stream);
+    float2 *tbl = static_cast<float2 *>(workspace);
+    float2 *tws = reinterpret_cast<float2 *>(static_cast<unsigned char *>(workspace) + rf_up256((size_t)m * sizeof(float2)));
+    float2 *out = static_cast<float2 *>(spec);
+    hipLaunchKernelGGL(rfft_twiddle_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, tbl, nfft);
+    if (int rc = pu::launch_check("rfft_twiddle_kernel")) return rc;
+    const int n2 = 1 << sh.l2, nr = 1 << sh.lr;
+    const size_t lds_rows = ((size_t)nr * (n2 + 1) + n2 / 2) * sizeof(float2);
+#define RF_ATTR(K, BYTES)                                                                                              \
+    do {                                                                                                               \
+        if ((BYTES) > 64 * 1024)                                                                                       \
+            PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                           (int)(BYTES)));                                                             \
+    } while (0)
+    if (sh.l1 == 0) {
+        if (dtype == PU_F32) {
+            RF_ATTR((rfft_rows_kernel<float, true>), lds_rows);
+            hipLaunchKernelGGL((rfft_rows_kernel<float, true>), dim3((unsigned)rows), dim3(RF_THREADS), lds_rows, s,
+                               static_cast<const float *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec);
+        } else {
+            RF_ATTR((rfft_rows_kernel<double, true>), lds_rows);
+            hipLaunchKernelGGL((rfft_rows_kernel<double, true>), dim3((unsigned)rows), dim3(RF_THREADS), lds_rows, s,
+                               static_cast<const double *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec);
+        }
+        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
+    } else {
+        const size_t lds_cols = ((size_t)RF_TILE + ((size_t)1 << sh.l1) / 2) * sizeof(float2);
+        const dim3 cgrid((unsigned)(rows * cgroups)), rgrid((unsigned)(rows * groups));
+        if (dtype == PU_F32) {
+            RF_ATTR((rfft_cols_kernel<float>), lds_cols);
+            hipLaunchKernelGGL((rfft_cols_kernel<float>), cgrid, dim3(RF_THREADS), lds_cols, s,
+                               static_cast<const float *>(x), n, ld, mean, sh, tbl, tws);
+        } else {
+            RF_ATTR((rfft_cols_kernel<double>), lds_cols);
+            hipLaunchKernelGGL((rfft_cols_kernel<double>), cgrid, dim3(RF_THREADS), lds_cols, s,
+                               static_cast<const double *>(x), n, ld, mean, sh, tbl, tws);
+        }
+        if (int rc = pu::launch_check("rfft_cols_kernel")) return rc;
+        RF_ATTR((rfft_rows_kernel<float, false>), lds_rows);
+        hipLaunchKernelGGL((rfft_rows_kernel<float, false>), rgrid, dim3(RF_THREADS), lds_rows, s,
+                           static_cast<const float *>(nullptr), n, ld, mean, sh, tbl, tws, out, ld_spec);
+        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
+    }
+#undef RF_ATTR
+    hipLaunchKernelGGL(rfft_split_kernel, dim3((unsigned)((m / 2 + 1 + 255) / 256), (unsigned)rows), dim3(256), 0, s, out,
+                       ld_spec, m, tbl);
+    return pu::launch_check("rfft_split_kernel");
+}
+
+}  // extern "C"

@@ -87,6 +87,12 @@ SIGNATURES = {
     "pu_fold_trials": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _sz,
                               _vp]),
     "pu_profile_chi2": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pu_rfft_workspace_bytes": (_sz, [_i64, _i64]),
+    "pu_rfft": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "pu_spectrum_normalize": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "pu_harmonic_search_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "pu_harmonic_search": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz,
+                                  _vp]),
     "pu_stream_create_cu_masked": (_i32, [_i32, ctypes.POINTER(_vp)]),
     "pu_stream_destroy": (_i32, [_vp]),
 }
@@ -98,6 +104,8 @@ INFO_FIELDS = ("ndm", "dm_tiles", "time_tiles", "trials_per_tile", "time_tile", 
 # pu_event (include/pulsarutils_hip.h): 40 bytes, no padding
 EVENT_DTYPE = np.dtype([("row", "<i4"), ("window", "<i4"), ("start", "<i8"), ("nbins", "<i8"), ("peak", "<i8"),
                         ("snr", "<f8")])
+# pu_spec_cand (include/pulsarutils_hip.h): 24 bytes, no padding
+SPEC_CAND_DTYPE = np.dtype([("row", "<i4"), ("level", "<i4"), ("bin", "<i8"), ("power", "<f4"), ("pad", "<f4")])
 KERNEL_NAMES = ("dedisp_kernel", "dedisp_f64_kernel", "dedisp_sub_kernel", "dedisp_sub_kernel (u16 slots)")
 
 
