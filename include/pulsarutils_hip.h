@@ -254,9 +254,10 @@ int pu_plan_kernel_times(pu_plan *plan, float *ms, int n);
 
 /* Diagnostics: in the PU_STAMPS build (make stamps -> libpulsarutils_hip_stamps.so) the
  * first call arms per-phase shader-clock stamps of the subband kernel and returns 0;
- * later calls synchronise, write up to ``n`` (<= 8) summed wave-cycle totals {stage
- * metadata, barrier A wait, build, barrier B wait, DMA issue, sum, epilogue, -} and
- * reset them.  Returns 0 in the production build. */
+ * later calls synchronise, write up to ``n`` (<= 16) summed wave-cycle totals {stall on
+ * the stage metadata after barrier A, barrier A wait, build, barrier B wait, DMA issue,
+ * sum, epilogue, -}, first of the waves that issue no DMA, then of the DMA-issuing
+ * waves, and reset them.  Returns 0 in the production build. */
 int pu_plan_stamps(pu_plan *plan, int64_t *out, int n);
 
 /* Introspection (tests / DESIGN.md): fills up to ``n`` of

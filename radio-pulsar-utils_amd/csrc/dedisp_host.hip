@@ -159,16 +159,17 @@ int pu_plan_stamps(pu_plan *p, int64_t *out, int n)
     PU_REQUIRE(p != nullptr && out != nullptr, "pu_plan_stamps: bad arguments");
     std::lock_guard<std::mutex> guard(p->lock);
 #ifdef PU_STAMPS
+    constexpr int kStamps = 16;  // 2 roles (other waves, DMA-issuing waves) x 8 phases
     if (!p->d_stamps) {
-        PU_TRY_HIP(hipMalloc((void **)&p->d_stamps, 8 * sizeof(uint64_t)));
-        PU_TRY_HIP(hipMemset(p->d_stamps, 0, 8 * sizeof(uint64_t)));
+        PU_TRY_HIP(hipMalloc((void **)&p->d_stamps, kStamps * sizeof(uint64_t)));
+        PU_TRY_HIP(hipMemset(p->d_stamps, 0, kStamps * sizeof(uint64_t)));
         return 0;  // armed: the next launches accumulate
     }
-    uint64_t h[8];
+    uint64_t h[kStamps];
     PU_TRY_HIP(hipDeviceSynchronize());
     PU_TRY_HIP(hipMemcpy(h, p->d_stamps, sizeof h, hipMemcpyDeviceToHost));
-    PU_TRY_HIP(hipMemset(p->d_stamps, 0, 8 * sizeof(uint64_t)));
-    const int m = std::min(n, 8);
+    PU_TRY_HIP(hipMemset(p->d_stamps, 0, kStamps * sizeof(uint64_t)));
+    const int m = std::min(n, kStamps);
     for (int i = 0; i < m; ++i) out[i] = (int64_t)h[i];
     return m;
 #else

@@ -269,7 +269,7 @@ struct SubArgs {
     int32_t nitems;         // work items (DM tiles x time tiles of this launch)
     int32_t base_bits;      // DMA row words: base = word & (2^base_bits - 1), cover = (word >> base_bits) x 256 B
     int32_t dt_major;       // item order: 0 = time tile major (DM tiles of a time tile share L2), 1 = DM tile major
-    void *stamps;           // diagnostic build (PU_STAMPS): 8 x u64 phase-cycle totals
+    void *stamps;           // diagnostic build (PU_STAMPS): 2 roles x 8 u64 phase-cycle totals
 };
 
 // Counted LDS wait, s_waitcnt lgkmcnt(N), that also "defines" the register it guards, so
@@ -1000,7 +1000,7 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
 
     // ---- stage loop.  Scalar metadata is loaded one step ahead (the stage records of k+1
     // and k+2, this wave's first DMA row base, slot record and window records), so the
-    // loads' latency overlaps the barrier waits instead of the phases.
+    // loads' latency overlaps a phase of work (kAhead, below) or at least the barrier waits.
     const int ns = ts.y;
     auto stage_at = [&](int k) { return ld_uniform(stages + ts.x + min(k, ns - 1)); };
     auto meta_of = [&](const i32x4 st) {
@@ -1009,30 +1009,66 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
     i32x4 st = stage_at(0), st1 = stage_at(1);
     if constexpr (kDma) issue_raw(st, bases_of(st), 0, rows_of(st));
 #ifdef PU_STAMPS
-    // diagnostic build only (make stamps): per-wave cycles per phase, summed over stages
+    // diagnostic build only (make stamps): per-wave cycles per phase, summed over stages.
+    // No stamp stands between the loop-top loads and barrier 1 (a stamp drains lgkmcnt:
+    // it would expose their latency before the barrier, on every wave): phase 1 runs from
+    // the end of the sum through the wave's own DMA wait and barrier 1; phase 0 is what the
+    // wave then waits for its scalar metadata (the clock is read before the wait, so two
+    // stamps back to back cost one scalar-cache round trip: the floor of phase 0).
     uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp = stamp(), tq;
 #define PU_PHASE(i) (tq = stamp(), ph[i] += tq - tp, tp = tq)
 #else
 #define PU_PHASE(i) ((void)0)
 #endif
+    // The scalar metadata a stage consumes right after barrier 1 is loaded a phase ahead and
+    // not just before that barrier, where the wave that arrives last (and releases it) has
+    // nothing to hide the latency behind before its first slot().  Measured: C2 13.52 ->
+    // 13.22 ms; the stamps do not show that stall on its own:
+    //  * rec0, the stage's first window record, is the record the previous stage's sum
+    //    loaded during its last group - the stages of a tile are consecutive in groups
+    //    (plan_sub; asserted by plan_check), so the row after a stage's last group is the
+    //    next stage's first.  Only the tile's first stage loads it here.
+    //  * m0, this wave's first slot record, and the stage record of k + 2 are loaded
+    //    right after barrier 2 of the previous stage, with its DMA issue: a whole sum ahead.
+    //    (Loading them at the sum's last group instead, m0 live across one group only, put
+    //    the loads on three paths of the group loop and spilled 40 more SGPRs: C2 13.98 vs
+    //    13.20 ms, parent 13.49; profiles/stage_metadata/.)
+    // kAhead: the G = 8 and the 16-bit-slot instantiations keep all three loads at the loop
+    // top, as before - their 16-word slot records / packed accumulators leave no room: loading
+    // ahead cost them SGPR spills (profiles/stage_metadata/code_object_metadata.txt).
+    constexpr bool kAhead = G < 8 && !S16;
+    rec_t rec0;
+    meta_t m0;
+    if constexpr (kAhead) {
+        rec0 = ld_uniform(recs + (size_t)st.x * W);
+        m0 = meta_of(st);
+    }
+    const int glt = a.ngroups - 1;  // the tile's last group: the last row of its records
     for (int k = 0; k < ns; ++k) {
-        const i32x4 st2 = stage_at(k + 2);
-        const meta_t m0 = meta_of(st);
-        const rec_t rec0 = ld_uniform(recs + (size_t)st.x * W);
-        PU_PHASE(0);
+        i32x4 st2;
+        meta_t m1;
+        if constexpr (!kAhead) {
+            st2 = stage_at(k + 2);
+            m0 = meta_of(st);
+            rec0 = ld_uniform(recs + (size_t)st.x * W);
+        }
         // This wave's LDS-DMA rows have landed before it arrives at the barrier.  Explicit:
         // a workgroup-scope __syncthreads does not wait for vmcnt on gfx950, and the
         // compiler's own LDS-DMA tracking puts its wait before this wave's first LDS read,
         // after the barrier - too late for the other waves that read these rows.
         asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-        PU_PHASE(7);
         __syncthreads();  // raw rows of stage k landed; every wave left the slot area
         PU_PHASE(1);
+        PU_PHASE(0);  // the stall on this stage's scalar metadata after the barrier
         const int vb1 = kDma && k + 1 < ns ? bases_of(st1) : 0;  // lands during the build
         if (!(skip & 1)) build(st, m0);
         PU_PHASE(2);
         __syncthreads();  // slots built; every wave left the raw rows
         PU_PHASE(3);
+        if constexpr (kAhead) {
+            m1 = meta_of(st1);  // past the tile's last stage: the clamped stage's, never used
+            st2 = stage_at(k + 2);
+        }
         if constexpr (kDma) {
             // the next stage's rows land while this stage is summed.  (Spreading these DMAs
             // over the sum's groups instead was measured slower, 20.6 vs 18.5 ms at C2: the
@@ -1056,12 +1092,17 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
             // two groups per iteration with ping-pong records (no per-group record copy).
             // A record is consumed only after the previous group's last lgkmcnt(0) (the empty
             // asm): hoisted into the trial loop, its scalar-load wait drained the LDS reads.
-            // The row past the stage's last group is a valid record (clamped index): loaded,
-            // never used.
-            rec_t ra = rec0;
+            // kAhead: the row past the stage's last group is the next stage's first record
+            // (rec0 of the next iteration, in ra or rb by the parity of the stage's group
+            // count); the index is clamped to the tile's last group, whose successor would be
+            // the next tile's row or, in the last tile, lie past the table.  Otherwise clamped
+            // to the stage's last group.  The clamped row is loaded again, never used.
+            rec_t ra = rec0, rb;
+            if constexpr (kAhead) rb = ra;  // read after the loop (a stage has >= 1 group: set there)
             const int gl = st.y - 1;
+            const int gc = kAhead ? glt : gl;
             for (int g = st.x; g < st.y; g += 2) {
-                rec_t rb = ld_uniform(recs + (size_t)min(g + 1, gl) * W);
+                rb = ld_uniform(recs + (size_t)min(g + 1, gc) * W);
                 if constexpr (S16) {
                     if (gc16 + 2 > F16) {
                         flush16<D>(lo16, hi16);
@@ -1074,18 +1115,22 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
                 }
                 asm volatile("" : "+s"(rb));
                 if (g + 1 > gl) break;
-                ra = ld_uniform(recs + (size_t)min(g + 2, gl) * W);
+                ra = ld_uniform(recs + (size_t)min(g + 2, gc) * W);
                 if constexpr (S16)
                     group_trials16<C>(lo16, rb, sb);
                 else
                     group_trials<C>(acc2, rb, sb);
                 asm volatile("" : "+s"(ra));
             }
+            if constexpr (kAhead) rec0 = ((st.y - st.x) & 1) ? rb : ra;
         }
+        // (a wave without trials sums nothing and uses no window record: its rec0 stays the
+        // tile's first, unused)
         if (dw >= 0) __builtin_amdgcn_s_setprio(0);
         PU_PHASE(5);
         st = st1;
         st1 = st2;
+        if constexpr (kAhead) m0 = m1;
     }
     if constexpr (S16) {
         if (active) s16_to_pairs<D>(lo16, hi16, acc2, lane);
@@ -1112,7 +1157,9 @@ __device__ __forceinline__ void sub_item(SubArgs &a, const i32x4 *__restrict__ t
     if (active && !(skip & 8)) write_outputs<float, float, K, D, PLANE, STATS>(acc, o, first, slot0, cnt, t0, tt, lane);
     PU_PHASE(6);
     if (lane == 0 && a.stamps) {
-        for (int i = 0; i < 8; ++i) atomicAdd(reinterpret_cast<unsigned long long *>(a.stamps) + i,
+        // two sets of totals by role: the DMA-issuing waves after the others
+        const int role = dw >= 0 ? 8 : 0;
+        for (int i = 0; i < 8; ++i) atomicAdd(reinterpret_cast<unsigned long long *>(a.stamps) + role + i,
                                               (unsigned long long)ph[i]);
     }
 #undef PU_PHASE

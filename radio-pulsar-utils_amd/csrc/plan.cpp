@@ -623,6 +623,13 @@ int plan_sub(const PlanProblem &pb, const int64_t *shifts, int G, int shape, siz
                 chans += gs;
                 ++g_end;
             }
+            // The stages of a tile are consecutive, and dedisp_sub_kernel relies on it twice
+            // (plan_check asserts both): in groups - the next stage begins at g_end (g =
+            // g_end below), so the window record after a stage's last group is the next
+            // stage's first, which the sum carries over instead of loading it again; and in
+            // slots - the next stage's s_begin is this stage's end, so the build's slot
+            // pointer, stepping past a stage's last slot, reads the next stage's records
+            // (or pad_slots' padding).
             stages.push_back(i32x4{g, g_end, s_begin, (int32_t)(slotmeta.size() / ms)});
             tile_stages[t].y++;
             if (dma) lds_tile += chans * ((row_len * eb + 255) / 256 * 256);  // DMA writes

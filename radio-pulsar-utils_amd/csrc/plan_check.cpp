@@ -2,19 +2,50 @@
 // of every planning path: linked with the library's own planner objects (planner.o, plan.o)
 // and no HIP library - `make plan_check`; the sources under AddressSanitizer and UBSan -
 // `make sanitize-plan`.  Prints each case's plan and table digest; exits non-zero if a case
-// fails to plan.  A case named like a key of tests/golden/plan_tables.json is that case
-// (tests/test_planner.py compares the digests).
+// fails to plan or a subband plan's stages break the order the kernel relies on
+// (stages_consecutive).  A case named like a key of tests/golden/plan_tables.json is that
+// case (tests/test_planner.py compares the digests).
 #include <algorithm>
 #include <cinttypes>
 #include <cstdio>
 #include <random>
 #include <vector>
 
+#include "dedisp_plan.h"
 #include "pulsarutils_hip.h"
 
 namespace {
 
 int failures = 0;
+
+// What dedisp_sub_kernel relies on in a subband plan (plan_sub states it where it pushes a
+// stage): the stages of a DM tile partition its groups in order - stage k + 1 begins at the
+// group where stage k ends, the first at group 0, the last ends at ngroups - so the window
+// record after a stage's last group is the next stage's first; and likewise its slots -
+// stage k + 1's slot records follow stage k's, so the build's read-ahead past a stage's
+// last slot stays inside the (padded) table.  The window records are ngroups x W x D words
+// per tile.  Returns the first violation, or nullptr.
+const char *stages_consecutive(const pu::PlanTables &t)
+{
+    if (t.group <= 1) return nullptr;  // channel mode: no stages
+    const int64_t wd = with_shape(t.shape, [](auto c) { return (int64_t) decltype(c)::W * decltype(c)::D; });
+    if ((int64_t)t.recs.size() != (int64_t)t.ndt * t.ngroups * wd) return "window records: not ngroups x W x D per tile";
+    if ((int64_t)t.tile_stages.size() != t.ndt) return "tile_stages: not one per tile";
+    for (const auto &ts : t.tile_stages) {
+        if (ts.y < 1 || ts.x < 0 || (int64_t)ts.x + ts.y > (int64_t)t.stages.size()) return "a tile's stage range";
+        for (int k = 0; k < ts.y; ++k) {
+            const auto &st = t.stages[(size_t)(ts.x + k)];
+            if (st.x >= st.y || st.z >= st.w) return "an empty stage";
+            if (st.w > t.nslots_total) return "a stage's slots past the table";
+            if (k == 0 ? st.x != 0 : st.x != t.stages[(size_t)(ts.x + k - 1)].y)
+                return "a stage does not begin at the group where the previous one ends";
+            if (k > 0 && st.z != t.stages[(size_t)(ts.x + k - 1)].w)
+                return "a stage's slots do not follow the previous stage's";
+        }
+        if (t.stages[(size_t)(ts.x + ts.y - 1)].y != t.ngroups) return "a tile's last stage does not end at ngroups";
+    }
+    return nullptr;
+}
 
 void run(const char *name, int dtype, int acc, int64_t nchan, int64_t n, const std::vector<int64_t> &shifts,
          pu_plan_opts opts)
@@ -27,6 +58,19 @@ void run(const char *name, int dtype, int acc, int64_t nchan, int64_t n, const s
         std::printf("%-28s FAILED rc %d: %s\n", name, rc, pu_last_error());
         ++failures;
         return;
+    }
+    {
+        pu::PlanProblem pb;
+        pu::PlanTables t;
+        const char *bad = "planning again failed";
+        if (pu::check_plan_args(dtype, acc, nchan, n, shifts.data(), ndm, &opts, pb) == PU_OK &&
+            pu::choose_plan(pb, shifts.data(), opts, t) == PU_OK)
+            bad = stages_consecutive(t);
+        if (bad) {
+            std::printf("%-28s FAILED stage order: %s\n", name, bad);
+            ++failures;
+            return;
+        }
     }
     std::printf("%-28s kernel %" PRId64 " group %" PRId64 " dm_tiles %" PRId64 " stages %" PRId64 " lds %" PRId64
                 " digest %016" PRIx64 "\n",
