@@ -529,23 +529,22 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
     """clean.py:276-351: stream a SIGPROC file through clean + DM search, chunk by chunk.
 
     Same chunking as the reference: ``step = max(int(chunk_length / tsamp) * 2, 128)``
-    samples (``chunk_length`` defaults to the whole-band delay at ``dmmax``), hop
-    ``step // 2`` (50 % overlap), chunks shorter than ``step // 2`` and chunks before
-    ``tmin`` skipped; channel mask from ``get_bad_chans`` (+ ``surelybad``);
+    samples (``chunk_length`` defaults to the whole-band delay at ``dmmax``) at 50 % overlap
+    (``filestream.overlapped_chunks``); channel mask from ``get_bad_chans`` (+ ``surelybad``);
     ``renormalize_data``; band flipped when ``foff < 0``; resampled by
     ``N = rint(new_sample_time / tsamp)`` when >= 2; ``dedispersion_search``.  All array
-    work stays in HBM (read_block_device -> renormalize_device -> HIP rebin -> search).
-    1-, 2- and 4-bit files are uploaded packed and unpacked to uint8 on the device
-    (``FilReader.device_block``); from there on they are 8-bit files.
+    work stays in HBM (``filestream.ChunkStream``, which uploads chunk k + 1 while chunk k is
+    worked on -> renormalize_device -> HIP rebin -> search).
 
     ``search_dtype``: the renormalised chunk is float64 (clean.py:73); ``"f64"``
     (default, the reference's behaviour, clean.py:346) searches it with float64
     accumulation in channel order (bit-exact series; certified statistics), ``"f32"``
     casts it to float32 on the device and searches with the float32 subband kernel (the
     north star's float32 summation-order tolerance; ~3x faster per chunk, but the file
-    pipeline is bound by the host read + PCIe copy either way).  ``zero_dm`` is renormalize_data's opt-in subtraction.
+    pipeline is bound by the host read + PCIe copy either way).  ``zero_dm`` is
+    renormalize_data's opt-in subtraction.
     ``profile``: a list that receives one dict of synchronised per-step timings (ms:
-    h2d, transpose, clean, cast, rebin, search) per chunk.
+    h2d, transpose, clean, rebin, cast, search) per chunk; no upload ahead then.
 
     Returns the list of candidate chunks (max S/N > ``snr_threshold``): dicts with
     istart, iend, t0, best DM, S/N, rebin and the full table.  With ``save_candidates``
@@ -566,17 +565,14 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
     """
     import os
     import pickle
-    import time
     from .dedispersion import _rebin_time_device, delta_delay, search_device
+    from .filestream import ChunkStream, StepTimer, bad_channel_mask, overlapped_chunks
     from .sigproc import FilReader
-    from .stats import get_bad_chans
     if search_dtype not in ("f32", "f64"):
         raise ValueError(f"search_dtype must be 'f32' or 'f64', got {search_dtype!r}")
     t = _hip.require_gpu()
     fname_root = os.path.basename(fname).split('.')[0]
-    mask = get_bad_chans(fname)
-    for bad_chan in surelybad:
-        mask[bad_chan] = True
+    mask = bad_channel_mask(fname, surelybad)
     fil = FilReader(fname)
     header = fil.header
     nsamples = header['nsamples']
@@ -602,114 +598,62 @@ def search_by_chunks(fname, chunk_length=None, new_sample_time=None, tmin=0, dmm
     trial_DMs = None
     plan = None
     candidates = []
-    chunks = []
-    for istart in range(0, nsamples, step // 2):
-        chunk_size = min(step, nsamples - istart)
-        if istart * sample_time < tmin or chunk_size < step // 2:
-            continue
-        chunks.append((istart, chunk_size))
+    chunks = overlapped_chunks(nsamples, step, sample_time, tmin)
     dev = t.device("cuda", t.cuda.current_device())
-    # Chunk k+1 is copied from the memory-mapped file to the device by a loader thread
-    # (a pageable H2D on a copy stream: the runtime's own staging, no extra host copy)
-    # while chunk k is cleaned and searched on the current stream.  With ``profile``
-    # every step is synchronised instead.
-    overlap = profile is None and len(chunks) > 1
-    copy_stream = t.cuda.Stream(device=dev) if overlap else None
-
-    def load(k):
-        istart, size = chunks[k]
-        tc = np.ascontiguousarray(fil._block_tc(istart, size))
-        with t.cuda.device(dev), t.cuda.stream(copy_stream):
-            dst = t.from_numpy(tc).to(dev)
-            ev = t.cuda.Event()
-            ev.record(copy_stream)
-        return dst, ev
-
-    pool = None
-    if overlap:
-        from concurrent.futures import ThreadPoolExecutor
-        pool = ThreadPoolExecutor(max_workers=1)
-        pending = pool.submit(load, 0)
-    for k, (istart, chunk_size) in enumerate(chunks):
-        t0 = istart * sample_time
-        iend = istart + chunk_size
-        marks = []
-
-        def mark(name):
-            if profile is not None:
-                t.cuda.synchronize()
-                marks.append((name, time.perf_counter()))
-
-        mark("start")
-        if overlap:
-            src, ev = pending.result()
-            if k + 1 < len(chunks):
-                pending = pool.submit(load, k + 1)
-            t.cuda.current_stream(dev).wait_event(ev)
-            src.record_stream(t.cuda.current_stream(dev))
-        else:
-            tc = np.ascontiguousarray(fil._block_tc(istart, chunk_size))
-            src = t.from_numpy(tc).to(dev)
-        mark("h2d")
-        block = fil.device_block(src)  # (1/2/4-bit files: uploaded packed, unpacked to uint8 here)
-        del src
-        mark("transpose")
-        if _hip.dtype_code(block.dtype) is None:
-            block = block.to(t.float64)
-        array, _ = renormalize_device(block, badchans_mask=mask, zero_dm=zero_dm)
-        del block
-        if foff < 0:
-            array = t.flip(array, dims=(0,)).contiguous()
-        mark("clean")
-        if N > 1:
-            array = _rebin_time_device(array, N)  # quick_resample of the float64 plane (clean.py:335-336)
-        mark("rebin")
-        array64 = array  # the candidate pickles hold the float64 plane, as in the reference
-        if search_dtype == "f32":
-            array = array.to(t.float32)
-        mark("cast")
-        nbin = array.shape[1]
-        if trial_DMs is None or plan is None or plan.nsamples != nbin:
-            trial_DMs = dedispersion_plan(nchan, dmmin, dmmax, start_freq, bandwidth, new_sample_time)
-            plan = None
-        (mx, sd, snr, win), plan = search_device(array, trial_DMs, nchan, start_freq, bandwidth, new_sample_time,
-                                                 acc=acc, plan=plan)
-        mark("search")
-        if profile is not None:
-            rec = {"istart": istart, "nsamples": chunk_size, "ndm": int(trial_DMs.size)}
-            rec.update({name: (tt - marks[i][1]) * 1e3 for i, (name, tt) in enumerate(marks[1:])})
-            profile.append(rec)
-        outs = (mx, sd, snr, win)
-        snr = _host(snr)
-        table = make_table({'DM': trial_DMs, 'max': _host(mx), 'std': _host(sd), 'snr': snr, 'rebin': _host(win)})
-        if np.any(snr > snr_threshold):
-            best = int(np.argmax(snr))
-            cand = {'istart': istart, 'iend': iend, 't0': t0, 'dm': float(trial_DMs[best]),
-                    'snr': float(snr[best]), 'rebin': int(table['rebin'][best]), 'table': table}
-            if find_pulses:
-                from .pulses import find_pulses as _find_pulses
-                pulses = _find_pulses(array, trial_DMs, nchan, start_freq, bandwidth, new_sample_time,
-                                      threshold=snr_threshold if pulse_threshold is None else pulse_threshold,
-                                      acc=acc, dm_tol=dm_tol, time_tol=time_tol, plan=plan, table=outs)
-                cols = {c: pulses[c] for c in pulses.colnames}
-                cols['time'] = cols['time'] + t0
-                cols['file_sample'] = istart + N * np.asarray(cols['sample'], dtype=np.int64)
-                cand['pulses'] = make_table(cols)
-            candidates.append(cand)
-            if save_candidates:
-                info = PulseInfo()
-                info.allprofs = _host(array64)
-                info.start_freq = start_freq
-                info.bandwidth = bandwidth
-                info.nbin = nbin
-                info.nchan = array.shape[0]
-                info.date = date
-                info.pulse_freq = 1 / (info.nbin * new_sample_time)
-                with open(f'{fname_root}_{istart}-{iend}.pkl', 'wb') as fh:
-                    pickle.dump(info, fh)
-        del array, array64
-    if pool is not None:
-        pool.shutdown(wait=True)
+    timer = StepTimer(profile)  # (with ``profile`` every step is synchronised and nothing is uploaded ahead)
+    with ChunkStream(fil, chunks, dev, prefetch=profile is None, timer=timer) as blocks:
+        for istart, chunk_size, block in blocks:
+            t0 = istart * sample_time
+            iend = istart + chunk_size
+            array, _ = renormalize_device(block, badchans_mask=mask, zero_dm=zero_dm)
+            del block
+            if foff < 0:
+                array = t.flip(array, dims=(0,)).contiguous()
+            timer.mark("clean")
+            if N > 1:
+                array = _rebin_time_device(array, N)  # quick_resample of the float64 plane (clean.py:335-336)
+            timer.mark("rebin")
+            array64 = array  # the candidate pickles hold the float64 plane, as in the reference
+            if search_dtype == "f32":
+                array = array.to(t.float32)
+            timer.mark("cast")
+            nbin = array.shape[1]
+            if trial_DMs is None or plan is None or plan.nsamples != nbin:
+                trial_DMs = dedispersion_plan(nchan, dmmin, dmmax, start_freq, bandwidth, new_sample_time)
+                plan = None
+            (mx, sd, snr, win), plan = search_device(array, trial_DMs, nchan, start_freq, bandwidth, new_sample_time,
+                                                     acc=acc, plan=plan)
+            timer.mark("search")
+            timer.record(istart, chunk_size, ndm=int(trial_DMs.size))
+            outs = (mx, sd, snr, win)
+            snr = _host(snr)
+            table = make_table({'DM': trial_DMs, 'max': _host(mx), 'std': _host(sd), 'snr': snr, 'rebin': _host(win)})
+            if np.any(snr > snr_threshold):
+                best = int(np.argmax(snr))
+                cand = {'istart': istart, 'iend': iend, 't0': t0, 'dm': float(trial_DMs[best]),
+                        'snr': float(snr[best]), 'rebin': int(table['rebin'][best]), 'table': table}
+                if find_pulses:
+                    from .pulses import find_pulses as _find_pulses
+                    pulses = _find_pulses(array, trial_DMs, nchan, start_freq, bandwidth, new_sample_time,
+                                          threshold=snr_threshold if pulse_threshold is None else pulse_threshold,
+                                          acc=acc, dm_tol=dm_tol, time_tol=time_tol, plan=plan, table=outs)
+                    cols = {c: pulses[c] for c in pulses.colnames}
+                    cols['time'] = cols['time'] + t0
+                    cols['file_sample'] = istart + N * np.asarray(cols['sample'], dtype=np.int64)
+                    cand['pulses'] = make_table(cols)
+                candidates.append(cand)
+                if save_candidates:
+                    info = PulseInfo()
+                    info.allprofs = _host(array64)
+                    info.start_freq = start_freq
+                    info.bandwidth = bandwidth
+                    info.nbin = nbin
+                    info.nchan = array.shape[0]
+                    info.date = date
+                    info.pulse_freq = 1 / (info.nbin * new_sample_time)
+                    with open(f'{fname_root}_{istart}-{iend}.pkl', 'wb') as fh:
+                        pickle.dump(info, fh)
+            del array, array64
     return candidates
 
 
@@ -738,22 +682,22 @@ def cleanup_data(fname, outname, nbits=8, chunksize=2**17, surelybad=(), baselin
     project's choice, with no reference counterpart.  ``nbits=32`` applies no scale or offset
     and writes the float32 of the renormalised plane.
 
-    Chunks are ``chunksize`` samples long and do not overlap; a tail shorter than ``chunksize
-    // 2`` is merged into the chunk before it (a file shorter than ``chunksize`` is one chunk).
-    Every input sample is written exactly once, in file channel order (no band flip: ``foff``
-    and ``fch1`` carry over); the output header is the input's with ``nbits`` replaced and
-    ``nifs = 1``.  Per chunk: upload -> ``FilReader.device_block`` -> ``renormalize_device``
-    -> quantise, transpose and pack on the device (``sigproc.quantize_pack_device``), so only
-    ``nbits / 8`` bytes per sample come back.  The device-to-host copy (pinned double buffer,
-    a copy stream) and the file write (one writer thread) of chunk k run while chunk k + 1 is
-    uploaded and cleaned.  ``profile``: a list that receives one dict of synchronised per-step
-    timings (ms: h2d, transpose, clean, quantize, d2h, write) per chunk; no overlap then.
+    Chunks are ``chunksize`` samples long and do not overlap (``filestream.tiled_chunks``: a
+    short tail is merged into the chunk before it).  Every input sample is written exactly
+    once, in file channel order (no band flip: ``foff`` and ``fch1`` carry over); the output
+    header is the input's with ``nbits`` replaced and ``nifs = 1``.  Per chunk: upload
+    (``filestream.ChunkStream``, on the current stream) -> ``renormalize_device`` -> quantise,
+    transpose and pack on the device (``sigproc.quantize_pack_device``), so only ``nbits / 8``
+    bytes per sample come back.  The device-to-host copy (pinned double buffer, a copy stream)
+    and the file write (one writer thread) of chunk k run while chunk k + 1 is uploaded and
+    cleaned.  ``profile``: a list that receives one dict of synchronised per-step timings (ms:
+    h2d, transpose, clean, quantize, d2h, write) per chunk; no overlap then.
 
     Returns a dict: nsamples, nchunks, nbits, mask, scale, offset (scale and offset None for
     ``nbits=32``)."""
-    import time
+    from .filestream import ChunkStream, StepTimer, bad_channel_mask, tiled_chunks
     from .sigproc import FilReader, FilWriter, quantize_pack_device
-    from .stats import get_bad_chans, get_spectral_stats
+    from .stats import get_spectral_stats
     nbits = int(nbits)
     if nbits not in (1, 2, 4, 8, 32):
         raise ValueError(f"cleanup_data: nbits must be 1, 2, 4, 8 or 32, got {nbits}")
@@ -762,9 +706,7 @@ def cleanup_data(fname, outname, nbits=8, chunksize=2**17, surelybad=(), baselin
         raise ValueError("cleanup_data: chunksize must be positive")
     t = _hip.require_gpu()
     mean_spec, std_spec = get_spectral_stats(fname)
-    mask = np.array(get_bad_chans(fname, stats=(mean_spec, std_spec)), dtype=bool)
-    for bad_chan in surelybad:
-        mask[bad_chan] = True
+    mask = bad_channel_mask(fname, surelybad, stats=(mean_spec, std_spec))
     fil = FilReader(fname)
     nsamples, nchan = fil.header["nsamples"], fil.header["nchans"]
     scale = offset = None
@@ -778,10 +720,7 @@ def cleanup_data(fname, outname, nbits=8, chunksize=2**17, surelybad=(), baselin
         scale = np.zeros(nchan, dtype=np.float64)
         scale[ok] = out_sigma / sig[ok]
         offset = np.full(nchan, out_mean, dtype=np.float64)
-    chunks = [(i, min(chunksize, nsamples - i)) for i in range(0, nsamples, chunksize)]
-    if len(chunks) > 1 and chunks[-1][1] < chunksize // 2:
-        last = chunks.pop()
-        chunks[-1] = (chunks[-1][0], chunks[-1][1] + last[1])
+    chunks = tiled_chunks(0, nsamples, chunksize)
     dev = t.device("cuda", t.cuda.current_device())
     dscale = t.from_numpy(scale).to(dev) if scale is not None else None
     doffset = t.from_numpy(offset).to(dev) if offset is not None else None
@@ -792,24 +731,10 @@ def cleanup_data(fname, outname, nbits=8, chunksize=2**17, surelybad=(), baselin
     pool = copy_stream = None
     pinned, busy = [None, None], [None, None]
 
-    def clean_chunk(istart, size, mark):
-        tc = np.ascontiguousarray(fil._block_tc(istart, size))
-        src = t.from_numpy(tc).to(dev)
-        mark("h2d")
-        block = fil.device_block(src)  # (1/2/4-bit files: uploaded packed, unpacked to uint8 here)
-        del src
-        mark("transpose")
-        if _hip.dtype_code(block.dtype) is None:
-            block = block.to(t.float64)
-        array, _ = renormalize_device(block, badchans_mask=mask, baseline_window=baseline_window,
-                                      cut_outliers=cut_outliers, zero_dm=zero_dm)
-        del block
-        mark("clean")
-        packed = quantize_pack_device(array, nbits, dscale, doffset)
-        mark("quantize")
-        return packed
-
-    with FilWriter(outname, fil.header, nbits=nbits) as writer:
+    timer = StepTimer(profile)
+    # (no upload ahead: it would change the stream order and the speed, so it needs its own measurement)
+    blocks = ChunkStream(fil, chunks, dev, prefetch=False, timer=timer)
+    with FilWriter(outname, fil.header, nbits=nbits) as writer, blocks:
         if overlap:
             from concurrent.futures import ThreadPoolExecutor
             pool = ThreadPoolExecutor(max_workers=1)
@@ -824,18 +749,16 @@ def cleanup_data(fname, outname, nbits=8, chunksize=2**17, surelybad=(), baselin
                 writer.write_rows(rows.numpy())
 
         try:
-            for k, (istart, size) in enumerate(chunks):
-                marks = []
-
-                def mark(name):
-                    if profile is not None:
-                        t.cuda.synchronize()
-                        marks.append((name, time.perf_counter()))
-
-                mark("start")
-                packed = clean_chunk(istart, size, mark)
+            for istart, size, block in blocks:  # (not enumerate: it would keep the block alive)
+                array, _ = renormalize_device(block, badchans_mask=mask, baseline_window=baseline_window,
+                                              cut_outliers=cut_outliers, zero_dm=zero_dm)
+                del block
+                timer.mark("clean")
+                packed = quantize_pack_device(array, nbits, dscale, doffset)
+                del array
+                timer.mark("quantize")
                 if overlap:
-                    slot = k % 2
+                    slot = istart // chunksize % 2  # (chunk k starts at k * chunksize)
                     if busy[slot] is not None:
                         busy[slot].result()  # the write of chunk k - 2 has left this buffer
                     cur = t.cuda.current_stream(dev)
@@ -852,13 +775,10 @@ def cleanup_data(fname, outname, nbits=8, chunksize=2**17, surelybad=(), baselin
                     busy[slot] = pool.submit(write_when_copied, done, rows, packed)
                 else:
                     rows = packed.cpu().numpy()
-                    mark("d2h")
+                    timer.mark("d2h")
                     writer.write_rows(rows)
-                    mark("write")
-                    if profile is not None:
-                        rec = {"istart": istart, "nsamples": size}
-                        rec.update({name: (tt - marks[i][1]) * 1e3 for i, (name, tt) in enumerate(marks[1:])})
-                        profile.append(rec)
+                    timer.mark("write")
+                    timer.record(istart, size)
                 del packed
             for fut in busy:
                 if fut is not None:

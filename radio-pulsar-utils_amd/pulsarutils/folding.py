@@ -107,12 +107,10 @@ def fold_file(fname, pulse_freq, nbin=128, ph0=0.0, chunksize=2**17, clean=True,
               zero_dm=False):
     """Fold a SIGPROC filterbank at ``pulse_freq`` (Hz) into a ``clean.PulseInfo``.
 
-    The file is streamed in non-overlapping chunks of ``chunksize`` samples (a tail shorter
-    than ``chunksize // 2`` is merged into the chunk before it); chunk k + 1 is uploaded by a
-    loader thread on a copy stream while chunk k is folded.  All array work stays in HBM;
-    1-, 2- and 4-bit files are uploaded packed and unpacked on the device
-    (``FilReader.device_block``).  The phase counts from the file's first sample, whatever
-    ``tmin``; samples ``i`` with ``tmin <= i * tsamp < tmax`` are folded.
+    The file is streamed in non-overlapping chunks of ``chunksize`` samples
+    (``filestream.tiled_chunks``); chunk k + 1 is uploaded while chunk k is folded
+    (``filestream.ChunkStream``) and all array work stays in HBM.  The phase counts from the
+    file's first sample, whatever ``tmin``; samples ``i`` with ``tmin <= i * tsamp < tmax`` are folded.
 
     ``clean=True``: each chunk goes through ``renormalize_device`` with the
     ``get_bad_chans`` (+ ``surelybad``) mask, as in ``search_by_chunks`` (``zero_dm`` is its
@@ -125,66 +123,28 @@ def fold_file(fname, pulse_freq, nbin=128, ph0=0.0, chunksize=2**17, clean=True,
     ``nbin, nchan, pulse_freq, ph0, start_freq, bandwidth, date`` set, plus the attribute
     ``counts``; it feeds ``clean.dedispersion_search(info, dmmin, dmmax)`` as it is."""
     from .clean import PulseInfo, renormalize_device
+    from .filestream import ChunkStream, bad_channel_mask, tiled_chunks
     from .sigproc import FilReader
-    from .stats import get_bad_chans
     nbin, chunksize = int(nbin), int(chunksize)
     if nbin < 1 or chunksize < 1:
         raise ValueError("fold_file: nbin and chunksize must be positive")
     t = _hip.require_gpu()
-    mask = np.array(get_bad_chans(fname), dtype=bool)
-    for bad_chan in surelybad:
-        mask[bad_chan] = True
+    mask = bad_channel_mask(fname, surelybad)
     fil = FilReader(fname)
     header = fil.header
     nsamples, tsamp, nchan = header["nsamples"], header["tsamp"], header["nchans"]
     i0 = min(nsamples, max(0, int(np.ceil(float(tmin) / tsamp))))
     i1 = nsamples if tmax is None else min(nsamples, max(i0, int(np.ceil(float(tmax) / tsamp))))
-    chunks = [(i, min(chunksize, i1 - i)) for i in range(i0, i1, chunksize)]
-    if len(chunks) > 1 and chunks[-1][1] < chunksize // 2:
-        last = chunks.pop()
-        chunks[-1] = (chunks[-1][0], chunks[-1][1] + last[1])
     dev = t.device("cuda", t.cuda.current_device())
     dphase = float(tsamp) * float(pulse_freq)
     sums = t.zeros((nchan, nbin), dtype=t.float64, device=dev)
     counts = t.zeros(nbin, dtype=t.int64, device=dev)
-    overlap = len(chunks) > 1
-    copy_stream = t.cuda.Stream(device=dev) if overlap else None
-
-    def load(k):
-        istart, size = chunks[k]
-        tc = np.ascontiguousarray(fil._block_tc(istart, size))
-        with t.cuda.device(dev), t.cuda.stream(copy_stream):
-            dst = t.from_numpy(tc).to(dev)
-            ev = t.cuda.Event()
-            ev.record(copy_stream)
-        return dst, ev
-
-    pool = None
-    try:
-        if overlap:
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(max_workers=1)
-            pending = pool.submit(load, 0)
-        for k, (istart, size) in enumerate(chunks):
-            if overlap:
-                src, ev = pending.result()
-                if k + 1 < len(chunks):
-                    pending = pool.submit(load, k + 1)
-                t.cuda.current_stream(dev).wait_event(ev)
-                src.record_stream(t.cuda.current_stream(dev))
-            else:
-                src = t.from_numpy(np.ascontiguousarray(fil._block_tc(istart, size))).to(dev)
-            block = fil.device_block(src)
-            del src
-            if _hip.dtype_code(block.dtype) not in (_hip.PU_U8, _hip.PU_F32, _hip.PU_F64):
-                block = block.to(t.float64)
+    with ChunkStream(fil, tiled_chunks(i0, i1, chunksize), dev, prefetch=True) as blocks:
+        for istart, _, block in blocks:
             if clean:
                 block, _ = renormalize_device(block, badchans_mask=mask, zero_dm=zero_dm)
             _fold_device(block, dphase, nbin, ph0, istart, sums, counts)
             del block
-    finally:
-        if pool is not None:
-            pool.shutdown(wait=True)
     s, c = sums.cpu().numpy(), counts.cpu().numpy()
     allprofs = np.zeros_like(s)
     hit = c > 0

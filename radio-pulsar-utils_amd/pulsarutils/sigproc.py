@@ -277,18 +277,23 @@ class FilReader:
             tc = _unpack(tc, self.nbits)
         return np.ascontiguousarray(tc.T)
 
-    def read_block_device(self, start, nsamps, device=None):
-        """(nchans, nsamps) device tensor: time-major bytes uploaded (packed ones still
-        packed), transposed by pu_transpose / unpacked by pu_unpack_transpose."""
+    def upload_block(self, start, nsamps, device=None, stream=None):
+        """The time-major rows of ``_block_tc`` as stored (packed bytes still packed) on the device: a
+        pageable copy from the memory map on ``stream`` (default: the current one)."""
         from . import _hip
         t = _hip.require_gpu()
         tc = np.ascontiguousarray(self._block_tc(start, nsamps))
-        src = t.from_numpy(tc).to(device or t.device("cuda", t.cuda.current_device()))
-        return self.device_block(src)
+        with t.cuda.stream(stream):  # (no stream: nothing to enter)
+            return t.from_numpy(tc).to(device or t.device("cuda", t.cuda.current_device()))
+
+    def read_block_device(self, start, nsamps, device=None):
+        """(nchans, nsamps) device tensor: time-major bytes uploaded (packed ones still
+        packed), transposed by pu_transpose / unpacked by pu_unpack_transpose."""
+        return self.device_block(self.upload_block(start, nsamps, device))
 
     def device_block(self, src):
         """Channel-major (nchans, nsamps) device tensor of an uploaded time-major block (the
-        rows of ``_block_tc``): ``uint8`` unpacked by pu_unpack_transpose for 1/2/4-bit
+        rows of ``upload_block``): ``uint8`` unpacked by pu_unpack_transpose for 1/2/4-bit
         files, the file's dtype transposed by pu_transpose otherwise."""
         if self.packed:
             return unpack_transpose_device(src, self.nbits, self.header["nchans"])
