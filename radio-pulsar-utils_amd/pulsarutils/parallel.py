@@ -1,25 +1,28 @@
-"""DM-trial sharding across GPUs (one process per GPU, torch.distributed over RCCL/xGMI).
+"""The search across GPUs (one process per GPU, torch.distributed over RCCL/xGMI), in two
+decompositions.
 
-The reference's only parallelism is numba ``prange`` over independent DM trials
-(``dedispersion.py:174,181``).  Here the same trial axis is split across ranks:
+``"dm"`` (:func:`pipelined_broadcast_search`): the reference's only parallelism is numba
+``prange`` over independent DM trials (``dedispersion.py:174,181``), and the same trial axis
+is split across ranks.  The filterbank is distributed from ``src`` in time chunks
+(``collective``: :func:`exchange_chunk`'s ``"broadcast"`` or, the default everywhere,
+``"scatter_allgather"``, whose traffic runs over every xGMI link of the mesh),
+each rank searches its contiguous slice of the trial grid, every time tile as soon as the
+columns it reads (its window plus the shift halo) have landed, and the per-trial statistics
+(max, std, snr, rebin) are all-gathered, so every rank ends with the reference's full-length
+result arrays.
 
-1. the filterbank is distributed from ``src`` (RCCL over xGMI; the data path of the
-   search itself has no other exchange).  :func:`pipelined_broadcast_search` cuts the
-   transfer into time chunks and starts the search of each time tile as soon as the
-   columns it reads (its window plus the shift halo) have landed, so the transfer of
-   later chunks overlaps the search of earlier ones.  Two exchanges per chunk
-   (``collective``): ``"broadcast"`` (one RCCL broadcast from ``src``) or
-   ``"scatter_allgather"`` (``src`` scatters 1/world of the chunk to every rank, then all
-   ranks all-gather it: the second step's traffic runs over every xGMI link of the mesh
-   instead of leaving ``src``'s links alone).  The default
-   everywhere (``DEFAULT_COLLECTIVE``) is ``"scatter_allgather"``;
-2. each rank searches its contiguous slice of the trial grid on its own GPU,
-3. the per-trial statistics (max, std, snr, rebin) are all-gathered, so every rank
-   ends with the reference's full-length result arrays.
+``"time"`` (:func:`tile_sharded_search`): every rank plans the whole trial grid, searches a
+contiguous range of its time tiles as their columns land, sends each trial's per-tile
+records to the trial's owner and finalizes its own trials.  Both run one chunk loop
+(:func:`_search_chunks`) over an exchange: the full copy by column prefix or interleaved
+ranges (:func:`_copy_exchange`), or the scatter of each rank's region (:func:`_sliced_scatter`).
 
 ``compute`` is injectable: the product path uses the HIP search; the CPU gloo tests
 pass the oracle to exercise the sharding / gather plumbing without a GPU.
 """
+import contextlib
+from types import SimpleNamespace
+
 import numpy as np
 
 
@@ -88,8 +91,7 @@ def exchange_chunk(buf, piece, rank, src, world, group=None, collective=DEFAULT_
     if collective == "broadcast" or world == 1:
         dist.broadcast(buf, src=src, group=group)
         return buf
-    if collective != "scatter_allgather":
-        raise ValueError(f"collective must be one of {COLLECTIVES}, got {collective!r}")
+    _check_collective(collective)
     m = buf.numel() // world
     if m * world != buf.numel() or piece.numel() != m:
         raise ValueError(f"scatter_allgather: buffer of {buf.numel()} elements is not {world} pieces of "
@@ -200,6 +202,7 @@ class PhaseEvents:
 
 
 _MASKED = {}  # (device index, reserved CUs) -> MaskedStream, kept for the process
+_NOTHING = contextlib.nullcontext()  # entered for phases=None and for the streams of a CPU tensor
 
 
 def _masked_stream(reserve, dev):
@@ -212,6 +215,147 @@ def _masked_stream(reserve, dev):
     if key not in _MASKED:
         _MASKED[key] = MaskedStream(reserve, dev)
     return _MASKED[key]
+
+
+def _world_rank(group):
+    import torch.distributed as dist
+    return (dist.get_world_size(group), dist.get_rank(group)) if dist.is_initialized() else (1, 0)
+
+
+def _check_rows(x, what):
+    if x.is_cuda and x.element_size() == 1 and x.shape[1] % 4 == 0 and (x.data_ptr() % 4 or x.stride(0) % 4):
+        # 8-bit LDS-DMA plans need dword-aligned rows; data is the receive buffer
+        raise ValueError(f"{what} of 8-bit data needs rows starting on 4-byte boundaries")
+
+
+def _check_collective(collective):
+    if collective not in COLLECTIVES:
+        raise ValueError(f"collective must be one of {COLLECTIVES}, got {collective!r}")
+
+
+@contextlib.contextmanager
+def _span(phases, name, stream):
+    phases.mark(name, stream)
+    yield
+    phases.mark(name, stream, end=True)
+
+
+def _phase(phases, name, stream):
+    """One span of ``phases`` (a :class:`PhaseEvents`, or None: nothing) on ``stream``."""
+    return _span(phases, name, stream) if phases is not None else _NOTHING
+
+
+class _Streams:
+    """The streams of one chunked search and the ordering edges between them (None, and
+    nothing done, for a CPU tensor):
+
+    * ``comm`` (packs, collectives, unpacks), ``comp`` (tile launches, records exchange,
+      finalize) and, with ``reserve_cus`` > 0, the CU-masked compute stream ``masked`` each
+      wait for ``cur``, the caller's current stream, at the start;
+    * before a chunk's launches the launch stream waits for ``comm`` behind the chunk's unpack
+      (``wait_stream``: an event); it is ``masked`` while a later chunk is still to come and
+      ``comp`` for the last, and after the second-to-last chunk ``comp`` waits for ``masked``;
+    * behind the last chunk the staging buffers get ``record_stream(comm)`` and ``then``
+      waits for ``comm``: ``cur`` in the pipelined search, before its finalize on ``comp``;
+      ``comp`` in the tile-sharded one, before its records exchange and finalize, which run
+      with ``comp`` as the current stream (:meth:`on`);
+    * :meth:`finish`: ``searcher.streams_done(comp)``, then ``(masked)``, where the searcher
+      has that method; then ``cur`` waits for the streams given: ``comp`` in the pipelined
+      search, ``comm`` then ``comp`` in the tile-sharded one."""
+
+    def __init__(self, data, reserve_cus=0):
+        import torch
+        self.cur = self.comm = self.comp = self.masked = None
+        if data.is_cuda:
+            self.cur = torch.cuda.current_stream(data.device)
+            self.comm, self.comp = torch.cuda.Stream(device=data.device), torch.cuda.Stream(device=data.device)
+            self.masked = _masked_stream(reserve_cus, data.device).stream if reserve_cus > 0 else None
+            for s in (self.comm, self.comp, self.masked):
+                if s is not None:
+                    s.wait_stream(self.cur)
+
+    def on(self, stream):
+        import torch
+        return _NOTHING if stream is None else torch.cuda.stream(stream)
+
+    def finish(self, searcher, *streams):
+        for s in (self.comp, self.masked):
+            if s is not None and hasattr(searcher, "streams_done"):
+                searcher.streams_done(s)
+        for s in streams:
+            if s is not None:
+                self.cur.wait_stream(s)
+
+
+def _copy_exchange(data, chunks, ready, rank, src, world, group, collective):
+    """The exchange that gives every rank all of ``src``'s ``data``.  Chunk k is a list of
+    column ranges (one: the column prefix; several: the interleaved full copy), packed into a
+    contiguous staging buffer on ``src``, exchanged (:func:`exchange_chunk`) and unpacked on the
+    receivers; ``ready(k)``: the caller's rule.  World 1 or ``src`` None: no collective, no mark."""
+    import torch
+    if world == 1 or src is None:
+        return SimpleNamespace(chunks=chunks, move=None, ready=ready, buffers=())
+    nchan = data.shape[0]
+    # staging holds whole chunks padded to a multiple of world elements (scatter pieces)
+    slen = -(-nchan * max(sum(c1 - c0 for c0, c1 in ranges) for ranges in chunks) // world) * world
+    staging = torch.empty(slen, dtype=data.dtype, device=data.device)
+    piece = staging.new_empty(slen // world) if collective == "scatter_allgather" else None
+
+    def move(k, comm, phases):
+        sizes = [nchan * (c1 - c0) for c0, c1 in chunks[k]]
+        blen = -(-sum(sizes) // world) * world
+        flat = staging[:blen]
+        views = [(held.view(nchan, -1), data[:, c0:c1])
+                 for held, (c0, c1) in zip(flat[:sum(sizes)].split(sizes), chunks[k])]
+        with _phase(phases, "exchange", comm):
+            if rank == src:
+                for held, cols in views:
+                    held.copy_(cols)
+            exchange_chunk(flat, piece[:blen // world] if piece is not None else None, rank, src, world,
+                           group=group, collective=collective)
+        with _phase(phases, "unpack", comm):
+            if rank != src:
+                for held, cols in views:
+                    cols.copy_(held)
+
+    return SimpleNamespace(chunks=chunks, move=move, ready=ready, buffers=(staging, piece))
+
+
+def _launch_ready(searcher, data, ready, mine, done, stream, phases):
+    """Launch my ready tiles not yet done on ``stream``, one call per contiguous run."""
+    ready = ready & mine & ~done
+    idx = np.flatnonzero(ready)
+    with _phase(phases, "search", stream):
+        for run in np.split(idx, np.flatnonzero(np.diff(idx) != 1) + 1) if idx.size else []:
+            searcher.tiles(data, int(run[0]), int(run[-1]) + 1, stream=stream)
+    done |= ready
+
+
+def _search_chunks(st, exchange, then, searcher, data, mine, phases):
+    """The chunk loop of both searches: chunk k of ``exchange`` (``chunks``, ``move(k, comm,
+    phases)`` or None, ``ready(k)``, ``buffers``) moves on the communication stream, the tiles of
+    ``mine`` (bool per tile) ready after it are launched behind it; in the end ``then`` waits
+    for ``comm``.  Returns the tiles launched; ``searcher`` None only takes part in the exchange."""
+    done = None if searcher is None else np.zeros(mine.size, dtype=bool)
+    nchunks = len(exchange.chunks)
+    for k in range(nchunks):
+        tstream = st.masked if st.masked is not None and k + 1 < nchunks else st.comp
+        if exchange.move is not None:
+            with st.on(st.comm):
+                exchange.move(k, st.comm, phases)
+        if searcher is None:
+            continue
+        if tstream is not None:
+            tstream.wait_stream(st.comm)  # the chunk has landed
+        _launch_ready(searcher, data, exchange.ready(k), mine, done, tstream, phases)
+        if st.masked is not None and k + 2 == nchunks:
+            st.comp.wait_stream(st.masked)  # the unmasked stream takes over for the last chunk
+    for b in exchange.buffers:
+        if b is not None and b.is_cuda:
+            b.record_stream(st.comm)
+    if then is not None:
+        then.wait_stream(st.comm)
+    return done
 
 
 def pipelined_broadcast_search(data, plan, out=None, workspace=None, src=0, chunks=8, group=None, searcher=None,
@@ -251,105 +395,24 @@ def pipelined_broadcast_search(data, plan, out=None, workspace=None, src=0, chun
     ``data`` tensor the same chunk / staging / unpack / ready-tile sequence runs
     synchronously, which is how the gloo tests drive the multi-rank branch on CPU.
     """
-    import contextlib
-
-    import torch
-    import torch.distributed as dist
-    cuda = data.is_cuda
-    dev = data.device
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    if cuda and data.element_size() == 1 and data.shape[1] % 4 == 0 and (data.data_ptr() % 4 or data.stride(0) % 4):
-        # 8-bit LDS-DMA plans need dword-aligned rows; data is the receive buffer
-        raise ValueError("pipelined search of 8-bit data needs rows starting on 4-byte boundaries")
-    nchan, n = data.shape
-    bounds = column_chunks(n, chunks)
+    world, rank = _world_rank(group)
+    _check_rows(data, "pipelined search")
+    _check_collective(collective)
+    bounds = column_chunks(data.shape[1], chunks)
     if searcher is None and plan is not None:
-        searcher = PlanSearcher(plan, out, workspace, dev)
-    masked = None
-    if cuda:
-        cur = torch.cuda.current_stream(dev)
-        comm = torch.cuda.Stream(device=dev)
-        comp = torch.cuda.Stream(device=dev)
-        comm.wait_stream(cur)
-        comp.wait_stream(cur)
-        if world > 1 and reserve_cus > 0 and searcher is not None and len(bounds) > 1:
-            masked = _masked_stream(reserve_cus, dev)
-            masked.stream.wait_stream(cur)
-    else:
-        cur = comm = comp = None
-    on_comm = (lambda: torch.cuda.stream(comm)) if cuda else contextlib.nullcontext
-    done = np.zeros(searcher.ntiles, dtype=bool) if searcher is not None else None
-    if collective not in COLLECTIVES:
-        raise ValueError(f"collective must be one of {COLLECTIVES}, got {collective!r}")
-    width = max(c1 - c0 for c0, c1 in bounds)
-    # staging holds whole chunks padded to a multiple of world elements (scatter pieces)
-    slen = -(-nchan * width // world) * world
-    staging = torch.empty(slen, dtype=data.dtype, device=dev) if world > 1 else None
-    piece = (torch.empty(slen // world, dtype=data.dtype, device=dev)
-             if world > 1 and collective == "scatter_allgather" else None)
-    for k, (c0, c1) in enumerate(bounds):
-        # tiles launched while later chunks are in flight use the masked stream
-        tstream = masked.stream if masked is not None and k + 1 < len(bounds) else comp
-        with on_comm():
-            if world > 1:
-                blen = -(-nchan * (c1 - c0) // world) * world
-                flat = staging[:blen]
-                buf = flat[:nchan * (c1 - c0)].view(nchan, c1 - c0)  # contiguous
-                if phases is not None:
-                    phases.mark("exchange", comm)
-                if rank == src:
-                    buf.copy_(data[:, c0:c1])
-                exchange_chunk(flat, piece[:blen // world] if piece is not None else None, rank, src, world,
-                               group=group, collective=collective)
-                if phases is not None:
-                    phases.mark("exchange", comm, end=True)
-                    phases.mark("unpack", comm)
-                if rank != src:
-                    data[:, c0:c1].copy_(buf)
-                if phases is not None:
-                    phases.mark("unpack", comm, end=True)
-            ev = None
-            if cuda:
-                ev = torch.cuda.Event()
-                ev.record(comm)
-        if searcher is None:
-            continue
-        if cuda:
-            tstream.wait_event(ev)
-        ready = searcher.ready(c1) & ~done
-        idx = np.flatnonzero(ready)
-        # contiguous runs of ready tiles, one launch each
-        if phases is not None:
-            phases.mark("search", tstream)
-        for run in np.split(idx, np.flatnonzero(np.diff(idx) != 1) + 1) if idx.size else []:
-            searcher.tiles(data, int(run[0]), int(run[-1]) + 1, stream=tstream)
-        if phases is not None:
-            phases.mark("search", tstream, end=True)
-        done |= ready
-        if masked is not None and k + 2 == len(bounds):
-            comp.wait_stream(masked.stream)  # the unmasked stream takes over for the last chunk
-    if cuda:
-        if staging is not None:
-            staging.record_stream(comm)
-        if piece is not None:
-            piece.record_stream(comm)
-        cur.wait_stream(comm)
+        searcher = PlanSearcher(plan, out, workspace, data.device)
+    st = _Streams(data, reserve_cus if world > 1 and searcher is not None and len(bounds) > 1 else 0)
+    exchange = _copy_exchange(data, [[b] for b in bounds], lambda k: searcher.ready(bounds[k][1]), rank, src, world,
+                              group, collective)
+    mine = None if searcher is None else np.ones(searcher.ntiles, dtype=bool)
+    done = _search_chunks(st, exchange, st.cur, searcher, data, mine, phases)
     if searcher is None:
         return None
     if not done.all():
         raise RuntimeError("pipelined search: time tiles left unsearched")
-    if phases is not None:
-        phases.mark("finalize", comp)
-    res = searcher.finalize(data, stream=comp)
-    if phases is not None:
-        phases.mark("finalize", comp, end=True)
-    if cuda:
-        if hasattr(searcher, "streams_done"):
-            searcher.streams_done(comp)
-            if masked is not None:
-                searcher.streams_done(masked.stream)
-        cur.wait_stream(comp)
+    with _phase(phases, "finalize", st.comp):
+        res = searcher.finalize(data, stream=st.comp)
+    st.finish(searcher, st.comp)
     return res
 
 
@@ -416,6 +479,88 @@ def _cols(c0, c1, n):
     return [(a, e)] if e <= n else [(a, n), (0, e - n)]
 
 
+def _sliced_scatter(data, tt, ntt, window, chunks, rank, src, world, group):
+    """The exchange that scatters to every rank only the columns its tiles read
+    (:func:`slice_regions`).  Chunk k is piece k of ``chunks`` of every rank's region, padded
+    to the widest (chunks of empty pieces are left out); a rank's tiles are ready once their
+    windows lie in the landed prefix of its region, and ``src``'s from the first chunk."""
+    import torch
+    import torch.distributed as dist
+    nchan, n = data.shape
+    regions = slice_regions(n, tt, ntt, world, *window)
+    K = max(1, int(chunks))
+    chunk_list = []
+    for k in range(K):
+        pieces = [None if rg is None else tuple(rg[0] + b for b in shard_bounds(rg[1], K, k)) for rg in regions]
+        w = max((pc[1] - pc[0] for pc in pieces if pc is not None), default=0)
+        if w > 0:
+            chunk_list.append((pieces, w))
+    width = max((w for _, w in chunk_list), default=1)
+    staging = torch.empty(world * nchan * width, dtype=data.dtype, device=data.device) if rank == src else None
+    piece = torch.empty(nchan * width, dtype=data.dtype, device=data.device)
+
+    def views(flat, pc):  # (columns of data, the same columns side by side in flat) of a piece
+        blk = flat[:nchan * (pc[1] - pc[0])].view(nchan, pc[1] - pc[0])
+        o = 0
+        for c0, c1 in _cols(pc[0], pc[1], n):
+            yield data[:, c0:c1], blk[:, o:o + c1 - c0]
+            o += c1 - c0
+
+    def move(k, comm, phases):
+        pieces, w = chunk_list[k]
+        m = nchan * w
+        with _phase(phases, "exchange", comm):
+            if rank == src:
+                for q, pc in enumerate(pieces):
+                    if q != src and pc is not None:  # src keeps its own columns
+                        for cols, held in views(staging[q * m:], pc):
+                            held.copy_(cols)
+            dist.scatter(piece[:m], list(staging[:world * m].split(m)) if rank == src else None, src=src,
+                         group=group)
+        with _phase(phases, "unpack", comm):
+            if rank != src and pieces[rank] is not None:
+                for cols, held in views(piece, pieces[rank]):
+                    cols.copy_(held)
+
+    def ready(k):
+        pc, rg = chunk_list[k][0][rank], regions[rank]
+        if rank == src or rg is None:
+            return np.full(ntt, rank == src)  # the source holds every column from the start
+        if rg[1] >= n:
+            return np.full(ntt, pc is not None and pc[1] >= rg[0] + rg[1])
+        return np.arange(ntt, dtype=np.int64) * tt + window[1] <= (pc[1] if pc is not None else rg[0])
+
+    return SimpleNamespace(chunks=chunk_list, move=move, ready=ready, buffers=(staging, piece))
+
+
+def _exchange_records(searcher, world, rank, group, stream, phases):
+    """Every trial's records of my tiles to the trial's owner; mine from every rank, into
+    ``searcher.records()`` (one all_to_all_single on ``stream``, the current stream)."""
+    import torch
+    import torch.distributed as dist
+    with _phase(phases, "records", stream):
+        rec = searcher.records()
+        R = rec.shape[2]
+        tb = [shard_bounds(searcher.ntiles, world, q) for q in range(world)]
+        db = [shard_bounds(searcher.ndm, world, q) for q in range(world)]
+        (my_t0, my_t1), (my_lo, my_hi) = tb[rank], db[rank]
+        send_parts = [rec[a:b, my_t0:my_t1].reshape(-1) if q != rank else rec.new_empty(0)
+                      for q, (a, b) in enumerate(db)]
+        in_splits = [p.numel() for p in send_parts]
+        out_splits = [0 if q == rank else (my_hi - my_lo) * (t1 - t0) * R for q, (t0, t1) in enumerate(tb)]
+        send = torch.cat(send_parts)
+        recv = rec.new_empty(sum(out_splits))
+        dist.all_to_all_single(recv, send, out_splits, in_splits, group=group)
+        off = 0
+        for q, (t0, t1) in enumerate(tb):
+            if out_splits[q]:
+                rec[my_lo:my_hi, t0:t1].copy_(recv[off:off + out_splits[q]].view(my_hi - my_lo, t1 - t0, R))
+            off += out_splits[q]
+        if rec.is_cuda:
+            send.record_stream(stream)
+            recv.record_stream(stream)
+
+
 def tile_sharded_search(data, plan, out=None, workspace=None, src=0, chunks=8, group=None, searcher=None,
                         collective=DEFAULT_COLLECTIVE, phases=None, full_copy=False):
     """Time-tile sharding: every rank holds the plan of the WHOLE trial grid and searches a
@@ -449,191 +594,45 @@ def tile_sharded_search(data, plan, out=None, workspace=None, src=0, chunks=8, g
     ``finalize_range(data, lo, hi, stream)`` and, for ``full_copy`` False,
     ``finalize_range_flagged(lo, hi, stream)``, ``exact_series(data, trials, t_begin, t_end, stream)``,
     ``series_stats(series, stream)``, ``nonfinite(x, stream)`` (0-d int tensor)."""
-    import contextlib
-
-    import torch
-    import torch.distributed as dist
-    cuda = data.is_cuda
-    dev = data.device
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    if cuda and data.element_size() == 1 and data.shape[1] % 4 == 0 and (data.data_ptr() % 4 or data.stride(0) % 4):
-        raise ValueError("tile-sharded search of 8-bit data needs rows starting on 4-byte boundaries")
-    if collective not in COLLECTIVES:
-        raise ValueError(f"collective must be one of {COLLECTIVES}, got {collective!r}")
-    nchan, n = data.shape
+    world, rank = _world_rank(group)
+    _check_rows(data, "tile-sharded search")
+    _check_collective(collective)
+    n = data.shape[1]
     if searcher is None:
-        searcher = PlanSearcher(plan, out, workspace, dev)
+        searcher = PlanSearcher(plan, out, workspace, data.device)
     ntt, tt = int(searcher.ntiles), int(searcher.tt_len)
-    my_t0, my_t1 = shard_bounds(ntt, world, rank)
     my_lo, my_hi = shard_bounds(searcher.ndm, world, rank)
     exchange = world > 1 and src is not None  # src None: data is already on every rank
     sliced = exchange and not full_copy
-    if cuda:
-        cur = torch.cuda.current_stream(dev)
-        comm = torch.cuda.Stream(device=dev)
-        comp = torch.cuda.Stream(device=dev)
-        comm.wait_stream(cur)
-        comp.wait_stream(cur)
-    else:
-        cur = comm = comp = None
-    on_comm = (lambda: torch.cuda.stream(comm)) if cuda else contextlib.nullcontext
-    on_comp = (lambda: torch.cuda.stream(comp)) if cuda else contextlib.nullcontext
+    st = _Streams(data)
     wa, wb = searcher.tile_window(0)
-    starts = np.arange(ntt, dtype=np.int64) * tt
     mine = np.zeros(ntt, dtype=bool)
-    mine[my_t0:my_t1] = True
-    done = np.zeros(ntt, dtype=bool)
+    mine[slice(*shard_bounds(ntt, world, rank))] = True
     if sliced:
-        regions = slice_regions(n, tt, ntt, world, wa, wb)
-        K = max(1, int(chunks))
-        # chunk k: piece k of every rank's region, padded to the widest
-        chunk_list = []
-        for k in range(K):
-            pieces = [None if rg is None else (rg[0] + shard_bounds(rg[1], K, k)[0], rg[0] + shard_bounds(rg[1], K, k)[1])
-                      for rg in regions]
-            w = max((b - a for pc in pieces if pc is not None for a, b in [pc]), default=0)
-            if w > 0:
-                chunk_list.append((pieces, w))
-        width = max((w for _, w in chunk_list), default=1)
-        staging = torch.empty(world * nchan * width, dtype=data.dtype, device=dev) if rank == src else None
-        piece = torch.empty(nchan * width, dtype=data.dtype, device=dev)
+        ex = _sliced_scatter(data, tt, ntt, (wa, wb), chunks, rank, src, world, group)
     else:
-        chunk_list = interleaved_chunks(n, tt, ntt, world, chunks if exchange else 1)
+        ranges = interleaved_chunks(n, tt, ntt, world, chunks if exchange else 1)
+        starts = np.arange(ntt, dtype=np.int64) * tt
         landed = np.zeros(-(-n // tt), dtype=bool)
-        width = max(sum(c1 - c0 for c0, c1 in ranges) for ranges in chunk_list)
-        slen = -(-nchan * width // world) * world
-        staging = torch.empty(slen, dtype=data.dtype, device=dev) if exchange else None
-        piece = (torch.empty(slen // world, dtype=data.dtype, device=dev)
-                 if exchange and collective == "scatter_allgather" else None)
-    for item in chunk_list:
-        with on_comm():
-            if phases is not None and exchange:
-                phases.mark("exchange", comm)
-            if sliced:
-                pieces, w = item
-                m = nchan * w
-                if rank == src:
-                    for q, pc in enumerate(pieces):
-                        if q == src or pc is None:
-                            continue  # src keeps its own columns
-                        blk = staging[q * m:q * m + nchan * (pc[1] - pc[0])].view(nchan, pc[1] - pc[0])
-                        o = 0
-                        for c0, c1 in _cols(pc[0], pc[1], n):
-                            blk[:, o:o + c1 - c0].copy_(data[:, c0:c1])
-                            o += c1 - c0
-                dist.scatter(piece[:m], list(staging[:world * m].split(m)) if rank == src else None, src=src,
-                             group=group)
-                if phases is not None:
-                    phases.mark("exchange", comm, end=True)
-                    phases.mark("unpack", comm)
-                pc = pieces[rank]
-                if rank != src and pc is not None:
-                    blk = piece[:nchan * (pc[1] - pc[0])].view(nchan, pc[1] - pc[0])
-                    o = 0
-                    for c0, c1 in _cols(pc[0], pc[1], n):
-                        data[:, c0:c1].copy_(blk[:, o:o + c1 - c0])
-                        o += c1 - c0
-                if phases is not None:
-                    phases.mark("unpack", comm, end=True)
-            elif exchange:
-                ranges = item
-                tot = nchan * sum(c1 - c0 for c0, c1 in ranges)
-                blen = -(-tot // world) * world
-                flat = staging[:blen]
-                views, off = [], 0
-                for c0, c1 in ranges:
-                    views.append((flat[off:off + nchan * (c1 - c0)].view(nchan, c1 - c0), c0, c1))
-                    off += nchan * (c1 - c0)
-                if rank == src:
-                    for v, c0, c1 in views:
-                        v.copy_(data[:, c0:c1])
-                exchange_chunk(flat, piece[:blen // world] if piece is not None else None, rank, src, world,
-                               group=group, collective=collective)
-                if phases is not None:
-                    phases.mark("exchange", comm, end=True)
-                    phases.mark("unpack", comm)
-                if rank != src:
-                    for v, c0, c1 in views:
-                        data[:, c0:c1].copy_(v)
-                if phases is not None:
-                    phases.mark("unpack", comm, end=True)
-            ev = None
-            if cuda:
-                ev = torch.cuda.Event()
-                ev.record(comm)
-        if sliced:
-            pc, rg = item[0][rank], regions[rank]
-            if rank == src:
-                ready = np.ones(ntt, dtype=bool)  # the source holds every column from the start
-            elif rg is None:
-                ready = np.zeros(ntt, dtype=bool)
-            elif rg[1] >= n:
-                ready = np.full(ntt, pc is not None and pc[1] >= rg[0] + rg[1])
-            else:
-                top = pc[1] if pc is not None else rg[0]
-                ready = starts + wb - starts[0] <= top
-        else:
-            for c0, c1 in item:
+
+        def ready(k):  # called once per chunk, in order
+            for c0, c1 in ranges[k]:
                 landed[c0 // tt:-(-c1 // tt)] = True
-            ready = ready_by_blocks(landed, tt, n, starts, wa - starts[0], wb - starts[0])
-        if cuda:
-            comp.wait_event(ev)
-        ready = ready & mine & ~done
-        idx = np.flatnonzero(ready)
-        if phases is not None:
-            phases.mark("search", comp)
-        for run in np.split(idx, np.flatnonzero(np.diff(idx) != 1) + 1) if idx.size else []:
-            searcher.tiles(data, int(run[0]), int(run[-1]) + 1, stream=comp)
-        if phases is not None:
-            phases.mark("search", comp, end=True)
-        done |= ready
-    if not done[my_t0:my_t1].all():
+            return ready_by_blocks(landed, tt, n, starts, wa, wb)
+
+        ex = _copy_exchange(data, ranges, ready, rank, src, world, group, collective)
+    done = _search_chunks(st, ex, st.comp, searcher, data, mine, phases)
+    if not done[mine].all():
         raise RuntimeError("tile-sharded search: time tiles left unsearched")
-    if cuda:
-        for b in (staging, piece):
-            if b is not None:
-                b.record_stream(comm)
-        comp.wait_stream(comm)
-    with on_comp():
+    with st.on(st.comp):
         if world > 1:
-            # every trial's records of my tiles to the trial's owner; mine from every rank
-            if phases is not None:
-                phases.mark("records", comp)
-            rec = searcher.records()
-            R = rec.shape[2]
-            tb = [shard_bounds(ntt, world, q) for q in range(world)]
-            db = [shard_bounds(searcher.ndm, world, q) for q in range(world)]
-            send_parts = [rec[a:b, my_t0:my_t1].reshape(-1) if q != rank else rec.new_empty(0)
-                          for q, (a, b) in enumerate(db)]
-            in_splits = [p.numel() for p in send_parts]
-            out_splits = [0 if q == rank else (my_hi - my_lo) * (t1 - t0) * R for q, (t0, t1) in enumerate(tb)]
-            send = torch.cat(send_parts)
-            recv = rec.new_empty(sum(out_splits))
-            dist.all_to_all_single(recv, send, out_splits, in_splits, group=group)
-            off = 0
-            for q, (t0, t1) in enumerate(tb):
-                if out_splits[q]:
-                    rec[my_lo:my_hi, t0:t1].copy_(recv[off:off + out_splits[q]].view(my_hi - my_lo, t1 - t0, R))
-                off += out_splits[q]
-            if cuda:
-                send.record_stream(comp)
-                recv.record_stream(comp)
-            if phases is not None:
-                phases.mark("records", comp, end=True)
-        if phases is not None:
-            phases.mark("finalize", comp)
-        if sliced:
-            res = _finalize_sliced(searcher, data, my_lo, my_hi, world, rank, ntt, tt, n, group, comp)
-        else:
-            res = searcher.finalize_range(data, my_lo, my_hi, stream=comp)
-        if phases is not None:
-            phases.mark("finalize", comp, end=True)
-    if cuda:
-        if hasattr(searcher, "streams_done"):
-            searcher.streams_done(comp)
-        cur.wait_stream(comm)
-        cur.wait_stream(comp)
+            _exchange_records(searcher, world, rank, group, st.comp, phases)
+        with _phase(phases, "finalize", st.comp):
+            if sliced:
+                res = _finalize_sliced(searcher, data, my_lo, my_hi, world, rank, ntt, tt, n, group, st.comp)
+            else:
+                res = searcher.finalize_range(data, my_lo, my_hi, stream=st.comp)
+    st.finish(searcher, st.comm, st.comp)
     return res, (my_lo, my_hi)
 
 
@@ -703,6 +702,20 @@ def _finalize_sliced(searcher, data, lo, hi, world, rank, ntt, tt, n, group, str
 DECOMPOSITIONS = ("dm", "time")
 
 
+def _prepared_plan(data, dms, tag, nchan, start_freq, bandwidth, sample_time, acc):
+    """``data`` prepared for the pipelined searches (they write it in place) and the cached
+    plan of the trials ``dms`` on it, ``tag`` in its identity (``dms`` None: no plan)."""
+    from . import _hip
+    from .dedispersion import _acc_code, _plan_for, _prepare_data
+    if not (data.is_cuda and data.is_contiguous()):
+        raise ValueError("pipelined sharded_search needs a contiguous device tensor (it is written in place)")
+    x = _prepare_data(data)
+    if dms is None:
+        return x, None
+    return x, _plan_for(x, lambda: _hip.shift_table(nchan, dms, start_freq, bandwidth, sample_time), _acc_code(acc),
+                        (tag, dms.tobytes(), float(start_freq), float(bandwidth), float(sample_time)))
+
+
 def sharded_search(data, trial_DMs, nchan, start_freq, bandwidth, sample_time, group=None, acc=None,
                    compute=None, broadcast=True, src=0, pipelined=False, chunks=8, collective=DEFAULT_COLLECTIVE,
                    decomposition="dm"):
@@ -720,8 +733,7 @@ def sharded_search(data, trial_DMs, nchan, start_freq, bandwidth, sample_time, g
     """
     import torch
     import torch.distributed as dist
-    world = dist.get_world_size(group)
-    rank = dist.get_rank(group)
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
     dms = np.asarray(trial_DMs, dtype=np.float64)
     lo, hi = shard_bounds(dms.size, world, rank)
     dev = data.device
@@ -731,46 +743,28 @@ def sharded_search(data, trial_DMs, nchan, start_freq, bandwidth, sample_time, g
         raise ValueError(f"decomposition must be one of {DECOMPOSITIONS}, got {decomposition!r}")
     if decomposition == "time" and not (pipelined and compute is None):
         raise ValueError("decomposition='time' needs the pipelined HIP search (pipelined=True, compute=None)")
+    res = None  # this rank's slice of the four statistics
     if decomposition == "time":
-        from . import _hip
-        from .dedispersion import _acc_code, _plan_for, _prepare_data
-        if not (data.is_cuda and data.is_contiguous()):
-            raise ValueError("pipelined sharded_search needs a contiguous device tensor (it is written in place)")
-        x = _prepare_data(data)
-        plan = _plan_for(x, lambda: _hip.shift_table(nchan, dms, start_freq, bandwidth, sample_time),
-                         _acc_code(acc), ("dm-grid", dms.tobytes(), float(start_freq), float(bandwidth),
-                                          float(sample_time)))
-        res, (a, b) = tile_sharded_search(x, plan, src=src if broadcast else None, chunks=chunks, group=group,
-                                          collective=collective)
-        for k in range(4):
-            local[k, :hi - lo] = res[k][lo:hi].to(torch.float64)
+        x, plan = _prepared_plan(data, dms, "dm-grid", nchan, start_freq, bandwidth, sample_time, acc)
+        res, _ = tile_sharded_search(x, plan, src=src if broadcast else None, chunks=chunks, group=group,
+                                     collective=collective)
+        res = [r[lo:hi] for r in res]
     elif pipelined and compute is None:
-        from . import _hip
-        from .dedispersion import _acc_code, _plan_for, _prepare_data
-        if not (data.is_cuda and data.is_contiguous()):
-            raise ValueError("pipelined sharded_search needs a contiguous device tensor (it is written in place)")
-        x = _prepare_data(data)
-        plan = None
-        if hi > lo:
-            sub = np.ascontiguousarray(dms[lo:hi])
-            plan = _plan_for(x, lambda: _hip.shift_table(nchan, sub, start_freq, bandwidth, sample_time),
-                             _acc_code(acc), ("dm-shard", sub.tobytes(), float(start_freq), float(bandwidth),
-                                              float(sample_time)))
+        x, plan = _prepared_plan(data, np.ascontiguousarray(dms[lo:hi]) if hi > lo else None, "dm-shard", nchan,
+                                 start_freq, bandwidth, sample_time, acc)
         if broadcast and world > 1:
             res = pipelined_broadcast_search(x, plan, src=src, chunks=chunks, group=group, collective=collective)
-        else:
-            res = plan.search(x) if plan is not None else None
-        if res is not None:
-            for k in range(4):
-                local[k, :hi - lo] = res[k].to(torch.float64)
+        elif plan is not None:
+            res = plan.search(x)
     else:
         if broadcast and world > 1:
             broadcast_filterbank(data, src=src, group=group, collective=collective)
         fn = compute or (lambda d, t: _hip_compute(d, t, nchan, start_freq, bandwidth, sample_time, acc))
         if hi > lo:
             res = fn(data, dms[lo:hi])
-            for k in range(4):
-                local[k, :hi - lo] = torch.as_tensor(res[k], dtype=torch.float64, device=dev)
+    if res is not None:
+        for k in range(4):
+            local[k, :hi - lo] = torch.as_tensor(res[k], dtype=torch.float64, device=dev)
     parts = [torch.empty_like(local) for _ in range(world)]
     dist.all_gather(parts, local, group=group)
     out = []

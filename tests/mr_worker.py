@@ -16,6 +16,9 @@ from garbage.  Checks (bit for bit):
     _dedispersion_search of each rank's trial slice (the same plans);
   * CASE C5m: the same with reserve_cus=8 (the CU-masked compute stream), outputs freed
     afterwards (the masked stream must outlive the tensors recorded on it).
+  * CASE C5p: as C5, and both pipelined searches once more with ``phases=PhaseEvents()``: the
+    same bits, and one exchange, unpack and search span per chunk of the search's chunk list,
+    one finalize span, one records span (tile-sharded search only), a finite step span and tail.
 MR_BACKEND=nccl (environment): an RCCL process group instead (WORLD 1 on the one GPU: the
 RCCL calls of the product path - broadcast on the communication stream, all_gather,
 barrier - with a single rank).
@@ -60,6 +63,7 @@ def main():
     c, ntrials, chunks, reserve = {
         "C5": (CONFIGS["C5"], 500, 5, 0),
         "C5m": (CONFIGS["C5"], 500, 4, 8),
+        "C5p": (CONFIGS["C5"], 500, 5, 0),
         "C3s": (replace(CONFIGS["C3"], nchan=512, nsamples=1 << 18), 625, 3, 0),
         # degenerate inputs (time decomposition): all-zero 8-bit data (every trial flagged:
         # std 0) and float32 data with one NaN (the NaN rule for every trial)
@@ -135,6 +139,8 @@ def main():
     del res, got, x
     torch.cuda.synchronize()
     torch.cuda.empty_cache()  # frees the tensors recorded on the (kept) masked stream
+    if case == "C5p":
+        check_phases(parallel, plan, received, x_ref, ref, src, chunks, collective, world, rank)
 
     # ---- sharded search (each rank its trial slice, all_gather of the statistics)
     x2 = received()
@@ -156,6 +162,42 @@ def main():
     dist.barrier()
     dist.destroy_process_group()
     print(f"RANK {rank} OK case {case} world {world} {backend} {collective} best DM {dms[best]:.3f} snr {snr[best]:.3f}", flush=True)
+
+
+def check_phases(parallel, plan, received, x_ref, ref, src, chunks, collective, world, rank):
+    """Both searches with real PhaseEvents at world > 1: the outputs are the one-GPU search's
+    bits, and times_ms() holds a span per chunk for exchange, unpack and search, one finalize
+    span, one records span for the tile-sharded search only, a finite step span and tail."""
+    import math
+
+    import numpy as np
+    import torch
+    n, tt, ntt = plan.nsamples, plan.info["time_tile"], plan.info["time_tiles"]
+    regions = [rg for rg in parallel.slice_regions(n, tt, ntt, world, *plan.tile_window(0)) if rg is not None]
+    nsliced = sum(any(b > a for a, b in (parallel.shard_bounds(rg[1], chunks, k) for rg in regions))
+                  for k in range(chunks))
+    runs = [("pipelined", len(parallel.column_chunks(n, chunks)), {}),
+            ("tile full_copy", len(parallel.interleaved_chunks(n, tt, ntt, world, chunks)), {"full_copy": True}),
+            ("tile sliced", nsliced, {"full_copy": False})]
+    for name, nchunks, kw in runs:
+        x, ph = received(), parallel.PhaseEvents()
+        if name == "pipelined":
+            res, (lo, hi) = parallel.pipelined_broadcast_search(x, plan, src=src, chunks=chunks, collective=collective,
+                                                                phases=ph), (0, plan.ndm)
+        else:
+            res, (lo, hi) = parallel.tile_sharded_search(x, plan, src=src, chunks=chunks, collective=collective,
+                                                         phases=ph, **kw)
+        torch.cuda.synchronize()
+        for k, (a, b) in enumerate(zip(ref, res)):
+            np.testing.assert_array_equal(a[lo:hi], b[lo:hi].cpu().numpy(), err_msg=f"rank {rank} {name} output {k}")
+        t = ph.times_ms()
+        print(f"rank {rank} {name}: {nchunks} chunks, phases {t}", flush=True)
+        for key in ("exchange_ms", "unpack_ms", "search_ms"):
+            assert len(t[key]) == nchunks, (name, key, t[key], nchunks)
+        assert len(t["finalize_ms"]) == 1, (name, t["finalize_ms"])
+        assert ("records_ms" in t) == (name != "pipelined") and len(t.get("records_ms", [0])) == 1, (name, t)
+        assert math.isfinite(t["step_span_ms"]) and math.isfinite(t["exposed_tail_ms"]), (name, t)
+        del res, x
 
 
 if __name__ == "__main__":

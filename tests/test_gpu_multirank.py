@@ -30,7 +30,9 @@ def _free_port():
     (2, "C5", "broadcast"), (3, "C5", "broadcast"), (2, "C3s", "broadcast"), (3, "C3s", "broadcast"),
     (2, "C5m", "broadcast"),
     # round 5: the mesh exchange (scatter 1/world of each chunk, then all-gather)
-    (2, "C5", "scatter_allgather"), (3, "C3s", "scatter_allgather"), (3, "C5m", "scatter_allgather")])
+    (2, "C5", "scatter_allgather"), (3, "C3s", "scatter_allgather"), (3, "C5m", "scatter_allgather"),
+    # both searches once more with phases=PhaseEvents(): a span per chunk and phase
+    (2, "C5p", "scatter_allgather")])
 def test_multirank_pipelined_and_sharded_on_one_gpu(gpu, world, case, collective):
     _run_ranks(world, case, collective, "dm")
 

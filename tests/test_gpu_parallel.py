@@ -56,6 +56,35 @@ def test_pipelined_tiles_equal_full_search(gpu, name, chunks):
         plan.search_tiles(xd, 0, ntt + 1, ws)
 
 
+@pytest.mark.parametrize("search", ["pipelined", "tile_sharded"])
+def test_world1_phase_events(gpu, search):
+    """World 1, no process group, real PhaseEvents (the path bench.py --full takes): both
+    pipelined searches give plan.search's bits and record one search span per chunk walked
+    (column_chunks for the pipelined search, a single chunk for the tile-sharded one with
+    src=None), one finalize span, and no exchange span - so no step span either."""
+    import torch
+    c = CONFIGS["C5"]
+    xd = synth.pulsar_filterbank_device(c)
+    dms = D.dedispersion_plan(c.nchan, c.dmmin, c.dmmax, c.start_freq, c.bandwidth, c.tsamp)[:300]
+    sh = _hip.shift_table(c.nchan, dms, c.start_freq, c.bandwidth, c.tsamp)
+    plan = _hip.Plan(_hip.dtype_code(xd.dtype), _hip.PU_ACC_NATIVE, c.nchan, c.nsamples, sh)
+    full = [o.cpu().numpy() for o in plan.search(xd)]
+    ph = parallel.PhaseEvents()
+    if search == "pipelined":
+        res, (lo, hi) = parallel.pipelined_broadcast_search(xd, plan, chunks=5, phases=ph), (0, dms.size)
+        nchunks = len(parallel.column_chunks(c.nsamples, 5))
+    else:
+        res, (lo, hi) = parallel.tile_sharded_search(xd, plan, src=None, chunks=5, phases=ph)
+        nchunks = 1
+    torch.cuda.synchronize()
+    assert (lo, hi) == (0, dms.size)
+    for a, b in zip(full, res):
+        np.testing.assert_array_equal(a[lo:hi], b[lo:hi].cpu().numpy())
+    t = ph.times_ms()
+    assert len(t["search_ms"]) == nchunks and len(t["finalize_ms"]) == 1, t
+    assert "exchange_ms" not in t and "step_span_ms" not in t, t
+
+
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_sharded_search_nccl_world1(gpu, pipelined):
     """parallel.sharded_search with the HIP compute (the product path) under a real

@@ -33,6 +33,30 @@ def _free_port():
     return p
 
 
+def _run_ranks(script, world, *args):
+    """One process per rank running ``script`` (plus ``args``) under the env:// rendezvous
+    variables; every rank must exit 0 and print "ok".  Returns the ranks' outputs."""
+    port = _free_port()
+    procs = []
+    for rank in range(world):
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                   LOCAL_RANK=str(rank), OMP_NUM_THREADS="1")
+        procs.append(subprocess.Popen([sys.executable, str(script), *args], env=env, stdout=subprocess.PIPE,
+                                      stderr=subprocess.STDOUT, text=True))
+    outs = []
+    for p in procs:
+        try:
+            out, _ = p.communicate(timeout=240)
+        except subprocess.TimeoutExpired:
+            p.kill()
+            out, _ = p.communicate()
+        outs.append(out)
+    for p, out in zip(procs, outs):
+        assert p.returncode == 0, out
+        assert "ok" in out
+    return outs
+
+
 WORKER = textwrap.dedent("""
     import os, sys
     sys.path[:0] = [{pkg!r}, {repo!r}]
@@ -70,24 +94,7 @@ def test_sharded_search_gloo(tmp_path, world, ndm, collective):
     result."""
     script = tmp_path / "worker.py"
     script.write_text(WORKER.format(pkg=PKG_DIR, repo=REPO, ndm=ndm, collective=collective))
-    port = _free_port()
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                   LOCAL_RANK=str(rank), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, _ = p.communicate()
-        outs.append(out)
-    for p, out in zip(procs, outs):
-        assert p.returncode == 0, out
-        assert "ok" in out
+    _run_ranks(script, world)
 
 
 class _FakePlan:
@@ -202,24 +209,7 @@ def test_pipelined_broadcast_gloo(tmp_path, world, src, n, chunks, smin, smax, d
     script = tmp_path / "pipe_worker.py"
     script.write_text(PIPE_WORKER.format(pkg=PKG_DIR, repo=REPO, n=n, src=src, chunks=chunks, smin=smin, smax=smax,
                                          dtype=dtype, collective=collective))
-    port = _free_port()
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                   LOCAL_RANK=str(rank), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, _ = p.communicate()
-        outs.append(out)
-    for p, out in zip(procs, outs):
-        assert p.returncode == 0, out
-        assert "ok" in out
+    _run_ranks(script, world)
 
 
 @pytest.mark.parametrize("n,tt,ntiles,world,chunks", [(1 << 20, 256, 4096, 8, 8), (1000, 256, 4, 3, 2),
@@ -382,21 +372,187 @@ def test_tile_sharded_search_gloo(tmp_path, world, src, n, ndm, chunks, smin, sm
     script = tmp_path / "tile_worker.py"
     script.write_text(TILE_WORKER.format(pkg=PKG_DIR, repo=REPO, n=n, ndm=ndm, src=src, chunks=chunks, smin=smin,
                                          smax=smax, collective=collective, nan=nan, full_copy=full_copy))
-    port = _free_port()
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                   LOCAL_RANK=str(rank), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, _ = p.communicate()
-        outs.append(out)
-    for p, out in zip(procs, outs):
-        assert p.returncode == 0, out
-        assert "ok" in out
+    _run_ranks(script, world)
+
+
+# ------------------------------------------------------------------ the exchange schedule, pinned
+
+SCHEDULE_FIXTURE = os.path.join(REPO, "tests", "golden", "parallel_schedule.json")
+LOGGED_COLLECTIVES = ("broadcast", "scatter", "all_gather_into_tensor", "all_to_all_single", "all_reduce")
+
+# world 3, a non-zero source, 3 chunks: the column prefix and the interleaved full copy under
+# both collectives, the sliced scatter with a shift halo; world 1: in process, no group
+SCHEDULE_CASES = {
+    "prefix-broadcast": dict(kind="prefix", world=3, src=1, collective="broadcast"),
+    "prefix-scatter_allgather": dict(kind="prefix", world=3, src=1, collective="scatter_allgather"),
+    "interleaved-broadcast": dict(kind="tile", world=3, src=2, collective="broadcast", full_copy=True),
+    "interleaved-scatter_allgather": dict(kind="tile", world=3, src=2, collective="scatter_allgather",
+                                          full_copy=True),
+    "sliced": dict(kind="tile", world=3, src=1, collective="scatter_allgather", full_copy=False),
+    "prefix-world1": dict(kind="prefix", world=1, src=0, collective="scatter_allgather"),
+    "tile-world1": dict(kind="tile", world=1, src=None, collective="scatter_allgather", full_copy=False),
+}
+
+
+class _LogPhases:
+    """Stands in for parallel.PhaseEvents: the two searches call nothing but mark."""
+
+    def __init__(self, log):
+        self.log = log
+
+    def mark(self, name, stream, end=False):
+        self.log.append(["mark", name, bool(end)])
+
+
+class _LogPrefixSearcher:
+    """pipelined_broadcast_search's searcher protocol; logs the launches, computes nothing.
+    18 tiles of 512 samples, windows [t0 - 308, t0 + 1551): tile 0 wraps modulo n."""
+
+    def __init__(self, log, n):
+        from pulsarutils.parallel import ready_tiles
+        self.log, self.plan, self._ready = log, _FakePlan(n, 512, -300, 700, 74), ready_tiles
+        self.ntiles = self.plan.info["time_tiles"]
+
+    def ready(self, landed):
+        return self._ready(self.plan, landed)
+
+    def tiles(self, d, b, e, stream=None):
+        self.log.append(["tiles", b, e])
+
+    def finalize(self, d, stream=None):
+        self.log.append(["final", "finalize"])
+        return "finalized"
+
+
+class _LogTileSearcher:
+    """tile_sharded_search's searcher protocol; logs the launches and the finalizes, computes
+    nothing.  Trials d % 3 == 1 are flagged and trial 0's owner reports a non-finite partial,
+    so the sliced finalize runs its counts all-gather, the non-finite all-reduce, the flagged
+    all-gather and the series all-gather."""
+
+    def __init__(self, log, n, tt, ndm, wa, wb):
+        import torch
+        self.torch, self.log, self.w = torch, log, (wa, wb)
+        self.ntiles, self.tt_len, self.ndm = -(-n // tt), tt, ndm
+        self.rec = torch.zeros((ndm, self.ntiles, 3), dtype=torch.float64)
+
+    def _outs(self, m):
+        t = self.torch
+        return [t.zeros(m, dtype=t.float64) for _ in range(3)] + [t.zeros(m, dtype=t.int32)]
+
+    def tile_window(self, i):
+        return (i * self.tt_len + self.w[0], i * self.tt_len + self.tt_len + self.w[1])
+
+    def tiles(self, d, b, e, stream=None):
+        self.log.append(["tiles", b, e])
+
+    def records(self):
+        return self.rec
+
+    def finalize_range(self, d, lo, hi, stream=None):
+        self.log.append(["final", "finalize_range", lo, hi])
+        return self._outs(self.ndm)
+
+    def finalize_range_flagged(self, lo, hi, stream=None):
+        self.log.append(["final", "finalize_range_flagged", lo, hi])
+        flagged = np.array([d for d in range(lo, hi) if d % 3 == 1], dtype=np.int32)
+        return self._outs(self.ndm), flagged, int(lo == 0 < hi)
+
+    def exact_series(self, d, trials, t_begin, t_end, stream=None):
+        return self.torch.zeros((len(trials), t_end - t_begin), dtype=self.torch.float64)
+
+    def series_stats(self, ser, stream=None):
+        return self._outs(ser.shape[0])
+
+    def nonfinite(self, x, stream=None):
+        return self.torch.tensor(0, dtype=self.torch.int32)
+
+
+def schedule_log(name, rank=0):
+    """Run SCHEDULE_CASES[name] on this rank with logging fakes and return the log, in call
+    order: ["coll", name, numel of the call's first tensor] for every torch.distributed
+    collective the module issues, ["tiles", b, e], ["final", name, ...], ["mark", name, end]."""
+    import torch
+    import torch.distributed as dist
+    from pulsarutils.parallel import pipelined_broadcast_search, tile_sharded_search
+    case = SCHEDULE_CASES[name]
+    log = []
+    real = {c: getattr(dist, c) for c in LOGGED_COLLECTIVES}
+
+    def logged(cname):
+        def call(tensor, *args, **kw):
+            log.append(["coll", cname, tensor.numel()])
+            return real[cname](tensor, *args, **kw)
+        return call
+
+    for c in LOGGED_COLLECTIVES:
+        setattr(dist, c, logged(c))
+    try:
+        if case["kind"] == "prefix":
+            nchan, n = 6, 9000
+            data = torch.arange(nchan * n, dtype=torch.float32).reshape(nchan, n) * (rank == case["src"])
+            res = pipelined_broadcast_search(data, None, src=case["src"], chunks=3, searcher=_LogPrefixSearcher(log, n),
+                                             collective=case["collective"], phases=_LogPhases(log))
+            assert res == "finalized"
+        else:
+            nchan, n, ndm = 5, 5000, 7
+            data = torch.arange(nchan * n, dtype=torch.float64).reshape(nchan, n) * (rank == case["src"])
+            s = _LogTileSearcher(log, n, 256, ndm, 40, 700)
+            _, (lo, hi) = tile_sharded_search(data, None, src=case["src"], chunks=3, searcher=s,
+                                              collective=case["collective"], phases=_LogPhases(log),
+                                              full_copy=case["full_copy"])
+            assert (lo, hi) == shard_bounds(ndm, case["world"], rank)
+    finally:
+        for c in LOGGED_COLLECTIVES:
+            setattr(dist, c, real[c])
+    return log
+
+
+def _schedule_logs(name):
+    """Every rank's log of one case: in process at world 1, else one gloo process per rank
+    (this file as the worker script)."""
+    import json
+    world = SCHEDULE_CASES[name]["world"]
+    if world == 1:
+        return [schedule_log(name)]
+    outs = _run_ranks(os.path.abspath(__file__), world, "worker", name)
+    return [json.loads(next(ln for ln in out.splitlines() if ln.startswith("LOG "))[4:]) for out in outs]
+
+
+@pytest.mark.parametrize("name", sorted(SCHEDULE_CASES))
+def test_exchange_schedule_unchanged(name):
+    """Which collectives are issued (order, sizes), which tiles are launched after which chunk,
+    which finalize runs and where the phases marks fall, per rank, equal the recorded schedule
+    (tests/golden/parallel_schedule.json; `python tests/test_parallel_gloo.py record` rewrites
+    it).  The logs depend on the shapes only.  World 1 (no process group): no collective and no
+    exchange or unpack mark, but the search marks of every chunk and the finalize marks."""
+    import json
+    from pulsarutils.parallel import column_chunks
+    logs = _schedule_logs(name)
+    with open(SCHEDULE_FIXTURE) as f:
+        want = json.load(f)[name]
+    assert logs == want
+    if SCHEDULE_CASES[name]["world"] == 1:
+        (log,) = logs
+        marks = [e[1:] for e in log if e[0] == "mark"]
+        assert not [e for e in log if e[0] == "coll"]
+        assert not [m for m in marks if m[0] in ("exchange", "unpack", "records")]
+        nchunks = len(column_chunks(9000, 3)) if name == "prefix-world1" else 1
+        assert marks == [["search", False], ["search", True]] * nchunks + [["finalize", False], ["finalize", True]]
+        assert sum(e[0] == "final" for e in log) == 1
+
+
+if __name__ == "__main__":
+    import json
+    if sys.argv[1] == "worker":
+        import torch.distributed as dist
+        dist.init_process_group("gloo")
+        rank = dist.get_rank()
+        print("LOG " + json.dumps(schedule_log(sys.argv[2], rank)))
+        dist.barrier()
+        dist.destroy_process_group()
+        print("rank", rank, "ok")
+    elif sys.argv[1] == "record":
+        with open(SCHEDULE_FIXTURE, "w") as f:
+            json.dump({name: _schedule_logs(name) for name in sorted(SCHEDULE_CASES)}, f, separators=(",", ":"))
+            f.write("\n")
