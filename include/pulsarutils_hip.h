@@ -618,6 +618,40 @@ size_t pu_rfft_workspace_bytes(int64_t rows, int64_t nfft);
 int pu_rfft(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *mean, int64_t nfft,
             void *spec, int64_t ld_spec, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Acceleration trials: time-domain resampling by nearest neighbour (the rule of peasoup and of
+ * sigproc's seek), and pu_rfft with that index map applied where its first pass loads its
+ * samples.  A signal of constant line-of-sight acceleration a is periodic again in the resampled
+ * series.  afac: device float64 [nacc], the dimensionless factors af = a * sample_time / (2 c), c =
+ * 299792458 m/s.  For a series of n samples (n <= 2^24) output sample i is input sample src(i):
+ *     p   = (double)(i * (i - n))                  int64 product; exact
+ *     q   = af * p                                 one float64 rounding, no fused multiply-add
+ *     s   = fmin(fmax(rint(q), -(double)i), (double)(n - 1 - i))
+ *     src = i + (int64)s
+ * rint rounds ties to even; fmax and fmin drop a NaN.  The end points stay fixed, af = 0 is the
+ * identity, and the clamp gives 0 <= src <= n - 1 for EVERY af (NaN and +-inf included): no input
+ * makes a kernel read outside its row.  The map is monotone while |af| n <= 1.
+ *
+ * pu_resample_accel: out[(a * rows + r) * ld_out + i] = x[r * ld + src_a(i)], out of x's dtype
+ * (PU_F32 / PU_F64), a plain gather; out must not overlap x.  PU_EUNSUPPORTED: dtype.  PU_EINVAL:
+ * rows, nacc or n < 0, rows or nacc >= 2^31, n > 2^24; ld < n or ld_out < n; a NULL or misaligned
+ * pointer; out == x.  PU_OK without a launch when rows, nacc or n is 0.
+ *
+ * pu_rfft_accel: pu_rfft over the nacc * rows virtual rows v = a * rows + r,
+ *     y[t] = (float)((double)x[r][src_a(t)] - mean[r])   for t < n,   0 for n <= t < nfft
+ * (the map takes n, not nfft), spec[v * ld_spec + k] as pu_rfft.  No resampled series is written:
+ * everything after the load is pu_rfft's code, so the result has the bits of pu_rfft on
+ * pu_resample_accel's output with the same mean (mean: [rows], NULL means 0), and at af = 0 the
+ * bits of pu_rfft on x.  workspace: pu_rfft_accel_workspace_bytes(rows, nacc, nfft) = pu_rfft's
+ * for nacc * rows rows.  Errors as pu_rfft with rows read as nacc * rows (at most 65535 per call);
+ * also PU_EINVAL for rows or nacc < 0 or >= 2^31 and for a NULL or misaligned afac.
+ * Both: all checked before any HIP call; asynchronous on stream. */
+int pu_resample_accel(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *afac,
+                      int64_t nacc, void *out, int64_t ld_out, void *stream);
+size_t pu_rfft_accel_workspace_bytes(int64_t rows, int64_t nacc, int64_t nfft);
+int pu_rfft_accel(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *mean,
+                  const double *afac, int64_t nacc, int64_t nfft, void *spec, int64_t ld_spec, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
 /* Power spectrum with the red noise taken out by a running median in blocks.  spec: device
  * complex64, rows x ld_spec (pu_rfft's output); nb = nfft / 2 bins k = 0 .. nb - 1 (the Nyquist
  * bin is dropped); block B: a power of two, 16 <= B <= min(1024, nb).  In float32, every step

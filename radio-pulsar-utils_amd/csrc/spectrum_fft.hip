@@ -1,4 +1,5 @@
-// Real-to-complex FFT of dedispersed series for gfx950: pu_rfft (include/pulsarutils_hip.h).
+// Real-to-complex FFT of dedispersed series for gfx950: pu_rfft, and the acceleration search's
+// pu_resample_accel and pu_rfft_accel (include/pulsarutils_hip.h).
 //
 // A row of nfft real samples is packed as M = nfft / 2 complex ones, z[j] = y[2j] + i y[2j+1]; the
 // complex transform Z of length M runs in LDS and a split step turns Z into the real-input
@@ -27,6 +28,14 @@
 // (k < nfft / 2) that rfft_twiddle_kernel makes at the start of the workspace with float64
 // sincospi rounded once to float32.  No fused multiply-add (-ffp-contract=off), no atomics, and
 // every operation's order is fixed by nfft: a row's bits depend on nothing but its samples.
+//
+// Acceleration trials: pu_rfft_accel transforms nacc x rows virtual rows, v = a rows + r, that
+// exist nowhere in memory.  The kernels that load samples take a map (RfPlain, RfAccel) that says
+// which row of x a virtual row reads and where in it sample t lies: accel_src(t, n, afac[a]), the
+// nearest-neighbour index of the time-domain resampling.  Everything after the load is the code
+// above, so the spectrum has the bits of pu_rfft on the series pu_resample_accel writes (the same
+// accel_src, as a plain gather).  The map is near the identity (|src - t| <= n / 4 over a whole
+// row, a step of one now and then), so a wave's loads stay contiguous but for those steps.
 //
 // LDS per workgroup: 8192 complex64 of data (64 KiB, + R pads) + N / 2 twiddles (<= 16 KiB):
 // at most 82 KiB of the CU's 160 KiB.
@@ -108,23 +117,55 @@ __device__ __forceinline__ void rf_lds_fft(float2 *s, const float2 *tw, int ln, 
     __syncthreads();
 }
 
+// Sample i of a series of n resampled at the factor af = accel * sample_time / (2 c) is sample
+// i + s of the input: s = rint(af i (i - n)) (ties to even), clamped so that 0 <= i + s <= n - 1
+// for every af (fmax and fmin drop a NaN: src = 0).  i (i - n) is exact in int64 and in float64
+// for n <= 2^24; one float64 product (no FMA: there is nothing to fuse), one rint.
+__device__ __forceinline__ int64_t accel_src(int64_t i, int64_t n, double af)
+{
+    const double q = af * (double)(i * (i - n));
+    const double s = fmin(fmax(rint(q), -(double)i), (double)(n - 1 - i));
+    return i + (int64_t)s;
+}
+
+// Where the first pass finds sample t of its row v.  RfPlain (pu_rfft): row v of x, sample t.
+struct RfPlain {
+    struct Row {
+        int64_t r;
+        __device__ __forceinline__ int64_t src(int64_t t) const { return t; }
+    };
+    __device__ __forceinline__ Row row(int64_t v, int64_t) const { return Row{v}; }
+};
+
+// RfAccel (pu_rfft_accel): virtual row v = a rows + r reads row r of x at accel_src(t, n, afac[a])
+struct RfAccel {
+    const double *afac;
+    int64_t rows;
+    struct Row {
+        int64_t r, n;
+        double af;
+        __device__ __forceinline__ int64_t src(int64_t t) const { return accel_src(t, n, af); }
+    };
+    __device__ __forceinline__ Row row(int64_t v, int64_t n) const { return Row{v % rows, n, afac[v / rows]}; }
+};
+
 // z[j] of a row: the packed, mean-subtracted, float32-rounded, zero-padded samples 2j, 2j + 1
-template <typename T>
-__device__ __forceinline__ float2 rf_sample(const T *__restrict__ row, int64_t n, double mu, int64_t j)
+template <typename T, typename ROW>
+__device__ __forceinline__ float2 rf_sample(const T *__restrict__ row, int64_t n, double mu, int64_t j, const ROW &m)
 {
     const int64_t t = 2 * j;
-    const float a = t < n ? (float)((double)row[t] - mu) : 0.0f;
-    const float b = t + 1 < n ? (float)((double)row[t + 1] - mu) : 0.0f;
+    const float a = t < n ? (float)((double)row[m.src(t)] - mu) : 0.0f;
+    const float b = t + 1 < n ? (float)((double)row[m.src(t + 1)] - mu) : 0.0f;
     return make_float2(a, b);
 }
 
 __device__ __forceinline__ int rf_brev(int i, int ln) { return (int)(__brev((unsigned)i) >> (32 - ln)); }
 
 // pass 1 of the four-step: columns j2 of z (N1 x N2) -> T[k1][j2] W_M^(j2 k1)
-template <typename T>
+template <typename T, typename MAP>
 __global__ void __launch_bounds__(RF_THREADS)
 rfft_cols_kernel(const T *__restrict__ x, int64_t n, int64_t ld, const double *__restrict__ mean, RfShape sh,
-                 const float2 *__restrict__ tbl, float2 *__restrict__ tws)
+                 const float2 *__restrict__ tbl, float2 *__restrict__ tws, MAP map)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
     float2 *s = reinterpret_cast<float2 *>(rf_smem);  // [N1][C]
@@ -133,12 +174,13 @@ rfft_cols_kernel(const T *__restrict__ x, int64_t n, int64_t ld, const double *_
     const int groups = n2 >> sh.lc;
     const int64_t r = blockIdx.x / groups;
     const int j20 = (int)(blockIdx.x % groups) << sh.lc;
-    const T *row = x + r * ld;
-    const double mu = mean ? mean[r] : 0.0;
+    const auto m = map.row(r, n);
+    const T *row = x + m.r * ld;
+    const double mu = mean ? mean[m.r] : 0.0;
     for (int j = threadIdx.x; j < n1 / 2; j += blockDim.x) tw[j] = tbl[(int64_t)j << (sh.lm + 1 - sh.l1)];
     for (int w = threadIdx.x; w < RF_TILE; w += blockDim.x) {
         const int c = w & cmask, j1 = w >> sh.lc;
-        s[w] = rf_sample(row, n, mu, (int64_t)j1 * n2 + j20 + c);
+        s[w] = rf_sample(row, n, mu, (int64_t)j1 * n2 + j20 + c, m);
     }
     rf_lds_fft<true>(s, tw, sh.l1, sh.lc);
     float2 *dst = tws + r * (int64_t)half;
@@ -150,11 +192,11 @@ rfft_cols_kernel(const T *__restrict__ x, int64_t n, int64_t ld, const double *_
 
 // pass 2 of the four-step (rows k1 of T -> Z[k1 + N1 k2]), or the whole transform of a short row
 // (FROM_X: N1 = 1, one row of z per workgroup)
-template <typename T, bool FROM_X>
+template <typename T, typename MAP, bool FROM_X>
 __global__ void __launch_bounds__(RF_THREADS)
 rfft_rows_kernel(const T *__restrict__ x, int64_t n, int64_t ld, const double *__restrict__ mean, RfShape sh,
                  const float2 *__restrict__ tbl, const float2 *__restrict__ tws, float2 *__restrict__ spec,
-                 int64_t ld_spec)
+                 int64_t ld_spec, MAP map)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
     const int n1 = 1 << sh.l1, n2 = 1 << sh.l2, pitch = n2 + 1, nr = 1 << sh.lr, half = 1 << sh.lm;
@@ -166,9 +208,10 @@ rfft_rows_kernel(const T *__restrict__ x, int64_t n, int64_t ld, const double *_
     for (int j = threadIdx.x; j < n2 / 2; j += blockDim.x) tw[j] = tbl[(int64_t)j << (sh.lm + 1 - sh.l2)];
     const int total = nr << sh.l2;
     if (FROM_X) {
-        const T *row = x + r * ld;
-        const double mu = mean ? mean[r] : 0.0;
-        for (int w = threadIdx.x; w < total; w += blockDim.x) s[w] = rf_sample(row, n, mu, w);
+        const auto m = map.row(r, n);
+        const T *row = x + m.r * ld;
+        const double mu = mean ? mean[m.r] : 0.0;
+        for (int w = threadIdx.x; w < total; w += blockDim.x) s[w] = rf_sample(row, n, mu, w, m);
     } else {
         const float2 *src = tws + r * (int64_t)half + (int64_t)k10 * n2;
         for (int w = threadIdx.x; w < total; w += blockDim.x) s[(w >> sh.l2) * pitch + (w & (n2 - 1))] = src[w];
@@ -211,9 +254,102 @@ rfft_split_kernel(float2 *__restrict__ spec, int64_t ld_spec, int64_t m, const f
     row[m - j] = make_float2(eb.x + pb.x, eb.y + pb.y);
 }
 
+// out[v][i] = x[v % rows][accel_src(i, n, afac[v / rows])]: the resampled series written out.
+// grid.y strides over the virtual rows v.
+template <typename T>
+__global__ void __launch_bounds__(256)
+resample_accel_kernel(const T *__restrict__ x, int64_t rows, int64_t n, int64_t ld, const double *__restrict__ afac,
+                      int64_t vrows, T *__restrict__ out, int64_t ld_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int64_t v = blockIdx.y; v < vrows; v += gridDim.y)
+        out[v * ld_out + i] = x[(v % rows) * ld + accel_src(i, n, afac[v / rows])];
+}
+
 bool rf_valid_nfft(int64_t nfft) { return nfft >= 256 && nfft <= ((int64_t)1 << 24) && (nfft & (nfft - 1)) == 0; }
 
 size_t rf_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// pu_rfft (MAP = RfPlain) and pu_rfft_accel (RfAccel) over vrows output rows: every check, then
+// the launches.  ``who`` names the entry point in the messages.
+template <typename MAP>
+int rf_transform(const char *who, const void *x, int dtype, int64_t vrows, int64_t n, int64_t ld, const double *mean,
+                 int64_t nfft, void *spec, int64_t ld_spec, void *workspace, size_t workspace_bytes, void *stream, MAP map)
+{
+    if (dtype != PU_F32 && dtype != PU_F64) {
+        pu::set_error("%s: unsupported dtype %d (a dedispersed series is float32 or float64)", who, dtype);
+        return PU_EUNSUPPORTED;
+    }
+    PU_REQUIRE(rf_valid_nfft(nfft), "%s: nfft %lld is not a power of two in [2^8, 2^24]", who, (long long)nfft);
+    PU_REQUIRE(vrows >= 0 && n >= 0 && n <= nfft, "%s: bad size (rows %lld, n %lld, nfft %lld)", who, (long long)vrows,
+               (long long)n, (long long)nfft);
+    PU_REQUIRE(ld >= n && ld_spec >= nfft / 2 + 1, "%s: leading dimension too small (ld %lld < n %lld or ld_spec "
+               "%lld < nfft / 2 + 1)", who, (long long)ld, (long long)n, (long long)ld_spec);
+    if (vrows == 0) return PU_OK;
+    const RfShape sh = rf_shape(nfft);
+    const int64_t m = nfft / 2;
+    const int64_t groups = sh.l1 ? ((int64_t)1 << (sh.l1 - sh.lr)) : 1, cgroups = sh.l1 ? ((int64_t)1 << (sh.l2 - sh.lc)) : 1;
+    PU_REQUIRE(vrows <= 65535 && vrows <= INT32_MAX / groups && vrows <= INT32_MAX / cgroups,
+               "%s: %lld rows exceed the grid limit (65535 per call)", who, (long long)vrows);
+    const size_t need = pu_rfft_workspace_bytes(vrows, nfft);
+    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
+               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", who, need, workspace_bytes);
+    PU_REQUIRE(x && spec, "%s: null pointer", who);
+    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % pu::elem_size(dtype) == 0 && reinterpret_cast<uintptr_t>(spec) % 8 == 0,
+               "%s: x or spec is not aligned to its element type", who);
+    hipStream_t s = pu::as_stream(stream);
+    float2 *tbl = static_cast<float2 *>(workspace);
+    float2 *tws = reinterpret_cast<float2 *>(static_cast<unsigned char *>(workspace) + rf_up256((size_t)m * sizeof(float2)));
+    float2 *out = static_cast<float2 *>(spec);
+    hipLaunchKernelGGL(rfft_twiddle_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, tbl, nfft);
+    if (int rc = pu::launch_check("rfft_twiddle_kernel")) return rc;
+    const int n2 = 1 << sh.l2, nr = 1 << sh.lr;
+    const size_t lds_rows = ((size_t)nr * (n2 + 1) + n2 / 2) * sizeof(float2);
+#define RF_ATTR(K, BYTES)                                                                                              \
+    do {                                                                                                               \
+        if ((BYTES) > 64 * 1024)                                                                                       \
+            PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                           (int)(BYTES)));                                                             \
+    } while (0)
+    if (sh.l1 == 0) {
+        if (dtype == PU_F32) {
+            RF_ATTR((rfft_rows_kernel<float, MAP, true>), lds_rows);
+            hipLaunchKernelGGL((rfft_rows_kernel<float, MAP, true>), dim3((unsigned)vrows), dim3(RF_THREADS), lds_rows, s,
+                               static_cast<const float *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec, map);
+        } else {
+            RF_ATTR((rfft_rows_kernel<double, MAP, true>), lds_rows);
+            hipLaunchKernelGGL((rfft_rows_kernel<double, MAP, true>), dim3((unsigned)vrows), dim3(RF_THREADS), lds_rows, s,
+                               static_cast<const double *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec, map);
+        }
+        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
+    } else {
+        const size_t lds_cols = ((size_t)RF_TILE + ((size_t)1 << sh.l1) / 2) * sizeof(float2);
+        const dim3 cgrid((unsigned)(vrows * cgroups)), rgrid((unsigned)(vrows * groups));
+        if (dtype == PU_F32) {
+            RF_ATTR((rfft_cols_kernel<float, MAP>), lds_cols);
+            hipLaunchKernelGGL((rfft_cols_kernel<float, MAP>), cgrid, dim3(RF_THREADS), lds_cols, s,
+                               static_cast<const float *>(x), n, ld, mean, sh, tbl, tws, map);
+        } else {
+            RF_ATTR((rfft_cols_kernel<double, MAP>), lds_cols);
+            hipLaunchKernelGGL((rfft_cols_kernel<double, MAP>), cgrid, dim3(RF_THREADS), lds_cols, s,
+                               static_cast<const double *>(x), n, ld, mean, sh, tbl, tws, map);
+        }
+        if (int rc = pu::launch_check("rfft_cols_kernel")) return rc;
+        // the second pass reads the workspace, never x: one instance serves both entry points
+        RF_ATTR((rfft_rows_kernel<float, RfPlain, false>), lds_rows);
+        hipLaunchKernelGGL((rfft_rows_kernel<float, RfPlain, false>), rgrid, dim3(RF_THREADS), lds_rows, s,
+                           static_cast<const float *>(nullptr), n, ld, mean, sh, tbl, tws, out, ld_spec, RfPlain{});
+        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
+    }
+#undef RF_ATTR
+    hipLaunchKernelGGL(rfft_split_kernel, dim3((unsigned)((m / 2 + 1 + 255) / 256), (unsigned)vrows), dim3(256), 0, s, out,
+                       ld_spec, m, tbl);
+    return pu::launch_check("rfft_split_kernel");
+}
+
+// rows and nacc of an acceleration call: both in [0, 2^31), so that their product is an int64
+bool rf_valid_trials(int64_t rows, int64_t nacc) { return rows >= 0 && nacc >= 0 && rows <= INT32_MAX && nacc <= INT32_MAX; }
 
 }  // namespace
 
@@ -232,74 +368,57 @@ size_t pu_rfft_workspace_bytes(int64_t rows, int64_t nfft)
 int pu_rfft(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *mean, int64_t nfft, void *spec,
             int64_t ld_spec, void *workspace, size_t workspace_bytes, void *stream)
 {
+    return rf_transform("pu_rfft", x, dtype, rows, n, ld, mean, nfft, spec, ld_spec, workspace, workspace_bytes, stream,
+                        RfPlain{});
+}
+
+size_t pu_rfft_accel_workspace_bytes(int64_t rows, int64_t nacc, int64_t nfft)
+{
+    if (!rf_valid_trials(rows, nacc)) return 0;
+    return pu_rfft_workspace_bytes(rows * nacc, nfft);
+}
+
+int pu_rfft_accel(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *mean, const double *afac,
+                  int64_t nacc, int64_t nfft, void *spec, int64_t ld_spec, void *workspace, size_t workspace_bytes,
+                  void *stream)
+{
+    PU_REQUIRE(rf_valid_trials(rows, nacc), "pu_rfft_accel: bad size (rows %lld, nacc %lld)", (long long)rows,
+               (long long)nacc);
+    PU_REQUIRE(rows * nacc <= 65535, "pu_rfft_accel: nacc %lld x rows %lld exceed the grid limit (65535 per call)",
+               (long long)nacc, (long long)rows);
+    PU_REQUIRE(afac || rows * nacc == 0, "pu_rfft_accel: null pointer (afac)");
+    PU_REQUIRE(reinterpret_cast<uintptr_t>(afac) % 8 == 0, "pu_rfft_accel: afac is not aligned to its element type");
+    return rf_transform("pu_rfft_accel", x, dtype, rows * nacc, n, ld, mean, nfft, spec, ld_spec, workspace,
+                        workspace_bytes, stream, RfAccel{afac, rows});
+}
+
+int pu_resample_accel(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *afac, int64_t nacc,
+                      void *out, int64_t ld_out, void *stream)
+{
     if (dtype != PU_F32 && dtype != PU_F64) {
-        pu::set_error("pu_rfft: unsupported dtype %d (a dedispersed series is float32 or float64)", dtype);
+        pu::set_error("pu_resample_accel: unsupported dtype %d (a dedispersed series is float32 or float64)", dtype);
         return PU_EUNSUPPORTED;
     }
-    PU_REQUIRE(rf_valid_nfft(nfft), "pu_rfft: nfft %lld is not a power of two in [2^8, 2^24]", (long long)nfft);
-    PU_REQUIRE(rows >= 0 && n >= 0 && n <= nfft, "pu_rfft: bad size (rows %lld, n %lld, nfft %lld)", (long long)rows,
-               (long long)n, (long long)nfft);
-    PU_REQUIRE(ld >= n && ld_spec >= nfft / 2 + 1, "pu_rfft: leading dimension too small (ld %lld < n %lld or ld_spec "
-               "%lld < nfft / 2 + 1)", (long long)ld, (long long)n, (long long)ld_spec);
-    if (rows == 0) return PU_OK;
-    const RfShape sh = rf_shape(nfft);
-    const int64_t m = nfft / 2;
-    const int64_t groups = sh.l1 ? ((int64_t)1 << (sh.l1 - sh.lr)) : 1, cgroups = sh.l1 ? ((int64_t)1 << (sh.l2 - sh.lc)) : 1;
-    PU_REQUIRE(rows <= 65535 && rows <= INT32_MAX / groups && rows <= INT32_MAX / cgroups,
-               "pu_rfft: %lld rows exceed the grid limit (65535 per call)", (long long)rows);
-    const size_t need = pu_rfft_workspace_bytes(rows, nfft);
-    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
-               "pu_rfft: workspace of %zu bytes (256-byte aligned) needed, got %zu", need, workspace_bytes);
-    PU_REQUIRE(x && spec, "pu_rfft: null pointer");
-    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % pu::elem_size(dtype) == 0 && reinterpret_cast<uintptr_t>(spec) % 8 == 0,
-               "pu_rfft: x or spec is not aligned to its element type");
-    hipStream_t s = pu::as_stream(stream);
-    float2 *tbl = static_cast<float2 *>(workspace);
-    float2 *tws = reinterpret_cast<float2 *>(static_cast<unsigned char *>(workspace) + rf_up256((size_t)m * sizeof(float2)));
-    float2 *out = static_cast<float2 *>(spec);
-    hipLaunchKernelGGL(rfft_twiddle_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, tbl, nfft);
-    if (int rc = pu::launch_check("rfft_twiddle_kernel")) return rc;
-    const int n2 = 1 << sh.l2, nr = 1 << sh.lr;
-    const size_t lds_rows = ((size_t)nr * (n2 + 1) + n2 / 2) * sizeof(float2);
-#define RF_ATTR(K, BYTES)                                                                                              \
-    do {                                                                                                               \
-        if ((BYTES) > 64 * 1024)                                                                                       \
-            PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                           (int)(BYTES)));                                                             \
-    } while (0)
-    if (sh.l1 == 0) {
-        if (dtype == PU_F32) {
-            RF_ATTR((rfft_rows_kernel<float, true>), lds_rows);
-            hipLaunchKernelGGL((rfft_rows_kernel<float, true>), dim3((unsigned)rows), dim3(RF_THREADS), lds_rows, s,
-                               static_cast<const float *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec);
-        } else {
-            RF_ATTR((rfft_rows_kernel<double, true>), lds_rows);
-            hipLaunchKernelGGL((rfft_rows_kernel<double, true>), dim3((unsigned)rows), dim3(RF_THREADS), lds_rows, s,
-                               static_cast<const double *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec);
-        }
-        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
-    } else {
-        const size_t lds_cols = ((size_t)RF_TILE + ((size_t)1 << sh.l1) / 2) * sizeof(float2);
-        const dim3 cgrid((unsigned)(rows * cgroups)), rgrid((unsigned)(rows * groups));
-        if (dtype == PU_F32) {
-            RF_ATTR((rfft_cols_kernel<float>), lds_cols);
-            hipLaunchKernelGGL((rfft_cols_kernel<float>), cgrid, dim3(RF_THREADS), lds_cols, s,
-                               static_cast<const float *>(x), n, ld, mean, sh, tbl, tws);
-        } else {
-            RF_ATTR((rfft_cols_kernel<double>), lds_cols);
-            hipLaunchKernelGGL((rfft_cols_kernel<double>), cgrid, dim3(RF_THREADS), lds_cols, s,
-                               static_cast<const double *>(x), n, ld, mean, sh, tbl, tws);
-        }
-        if (int rc = pu::launch_check("rfft_cols_kernel")) return rc;
-        RF_ATTR((rfft_rows_kernel<float, false>), lds_rows);
-        hipLaunchKernelGGL((rfft_rows_kernel<float, false>), rgrid, dim3(RF_THREADS), lds_rows, s,
-                           static_cast<const float *>(nullptr), n, ld, mean, sh, tbl, tws, out, ld_spec);
-        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
-    }
-#undef RF_ATTR
-    hipLaunchKernelGGL(rfft_split_kernel, dim3((unsigned)((m / 2 + 1 + 255) / 256), (unsigned)rows), dim3(256), 0, s, out,
-                       ld_spec, m, tbl);
-    return pu::launch_check("rfft_split_kernel");
+    PU_REQUIRE(rf_valid_trials(rows, nacc) && n >= 0 && n <= ((int64_t)1 << 24),
+               "pu_resample_accel: bad size (rows %lld, nacc %lld, n %lld; n <= 2^24)", (long long)rows, (long long)nacc,
+               (long long)n);
+    PU_REQUIRE(ld >= n && ld_out >= n, "pu_resample_accel: leading dimension too small (ld %lld or ld_out %lld < n %lld)",
+               (long long)ld, (long long)ld_out, (long long)n);
+    const int64_t vrows = rows * nacc;
+    if (vrows == 0 || n == 0) return PU_OK;
+    PU_REQUIRE(x && afac && out && x != out, "pu_resample_accel: null pointer, or out is x (not in place)");
+    const size_t es = pu::elem_size(dtype);
+    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % es == 0 && reinterpret_cast<uintptr_t>(out) % es == 0 &&
+                   reinterpret_cast<uintptr_t>(afac) % 8 == 0,
+               "pu_resample_accel: x, out or afac is not aligned to its element type");
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(vrows < 65535 ? vrows : 65535));
+    if (dtype == PU_F32)
+        hipLaunchKernelGGL(resample_accel_kernel<float>, grid, dim3(256), 0, pu::as_stream(stream),
+                           static_cast<const float *>(x), rows, n, ld, afac, vrows, static_cast<float *>(out), ld_out);
+    else
+        hipLaunchKernelGGL(resample_accel_kernel<double>, grid, dim3(256), 0, pu::as_stream(stream),
+                           static_cast<const double *>(x), rows, n, ld, afac, vrows, static_cast<double *>(out), ld_out);
+    return pu::launch_check("resample_accel_kernel");
 }
 
 }  // extern "C"

@@ -89,6 +89,9 @@ SIGNATURES = {
     "pu_profile_chi2": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pu_rfft_workspace_bytes": (_sz, [_i64, _i64]),
     "pu_rfft": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "pu_resample_accel": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "pu_rfft_accel_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "pu_rfft_accel": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _sz, _vp]),
     "pu_spectrum_normalize": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "pu_harmonic_search_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pu_harmonic_search": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz,

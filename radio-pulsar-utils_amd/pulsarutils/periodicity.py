@@ -24,10 +24,18 @@ the highest harmonic has (a fundamental-based index would smear it over ``H`` bi
 candidate of its level when its sum is above the level's threshold, above its left neighbour and
 not below its right one.  Under noise ``S_l`` is Erlang(``H``) distributed: :func:`erlang_logsf`.
 
+Acceleration trials (``pu_resample_accel``, ``pu_rfft_accel``): a pulsar in a binary drifts across
+Fourier bins; resampling the series in time at its line-of-sight acceleration ``a`` makes it
+periodic again.  With ``af = a sample_time / (2 c)``, output sample ``i`` of ``n`` is input sample
+``i + rint(af i (i - n))`` (nearest neighbour, clamped into the row: :func:`resample_indices`).
+:func:`acceleration_search` runs the chain above over (acceleration, row) pairs, the index map
+applied where the FFT's first pass loads its samples.  A constant acceleration only.
+
 Conventions are ``folding``'s: numpy in -> numpy out, CUDA tensor in -> tensors out, a 1-D array
 is one row.  Importable without a GPU: :func:`next_nfft`, :func:`harmonic_bins`,
 :func:`erlang_logsf`, :func:`power_threshold`, :func:`sigma_from_logp`, :func:`logp_from_sigma`,
-:func:`bin_ranges` and :func:`sift_candidates` are pure numpy; the rest runs HIP kernels and
+:func:`bin_ranges`, :func:`sift_candidates`, :func:`accel_factor`, :func:`resample_indices` and
+:func:`acceleration_grid` are pure numpy; the rest runs HIP kernels and
 raises ``HipBackendError`` without the library or a GPU.
 """
 import ctypes
@@ -226,6 +234,55 @@ def sift_candidates(cands, tobs, max_ratio=16):
     return out
 
 
+# ------------------------------------------------------------------ acceleration trials (numpy)
+
+C_LIGHT = 299792458.0  # m / s
+MAX_ACCEL_TRIALS = 65535
+
+
+def accel_factor(accel, sample_time):
+    """The dimensionless factor ``af = accel * sample_time / (2 c)`` of an acceleration in m/s^2
+    (float64; an array gives an array)."""
+    sample_time = float(sample_time)
+    if not sample_time > 0:
+        raise ValueError("accel_factor: sample_time must be positive")
+    return np.asarray(accel, dtype=np.float64) * sample_time / (2.0 * C_LIGHT)
+
+
+def resample_indices(n, af):
+    """``src``, int64 ``(n,)``: sample ``i`` of a series of ``n`` resampled at the factor ``af`` is
+    sample ``src[i] = i + clamp(rint(af i (i - n)))`` of the input (nearest neighbour; the clamp
+    keeps ``0 <= src <= n - 1`` for every ``af``, NaN and inf included; include/pulsarutils_hip.h).
+    This is the map ``pu_resample_accel`` and ``pu_rfft_accel`` apply, step for step."""
+    n = int(n)
+    if n < 0 or n > MAX_NFFT:
+        raise ValueError("resample_indices: n must be in [0, 2^24]")
+    i = np.arange(n, dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.float64(af) * (i * (i - n)).astype(np.float64)
+        s = np.fmin(np.fmax(np.rint(q), -i.astype(np.float64)), (n - 1 - i).astype(np.float64))
+    return i + s.astype(np.int64)
+
+
+def acceleration_grid(amax, tobs, ftop, drift_bins=1.0):
+    """Trial accelerations (m/s^2, float64, ascending) from ``-amax`` to ``amax`` at least:
+    ``step * (-k .. k)`` with ``step = drift_bins c / (ftop tobs^2)`` and ``k = ceil(amax / step)``,
+    so the grid is symmetric and contains 0.  A signal at ``ftop`` Hz (the highest harmonic to be
+    summed) drifts ``ftop a tobs^2 / c`` Fourier bins under the acceleration ``a``: between two
+    trials it is left with at most ``drift_bins / 2``.  ``ValueError`` for a non-positive argument
+    or more than 65535 trials."""
+    amax, tobs, ftop, drift_bins = float(amax), float(tobs), float(ftop), float(drift_bins)
+    if not all(math.isfinite(v) and v > 0 for v in (amax, tobs, ftop, drift_bins)):
+        raise ValueError("acceleration_grid: amax, tobs, ftop and drift_bins must be positive")
+    step = drift_bins * C_LIGHT / (ftop * tobs * tobs)
+    steps = amax / step if step > 0 else math.inf
+    k = math.ceil(steps) if steps <= MAX_ACCEL_TRIALS else MAX_ACCEL_TRIALS
+    if 2 * k + 1 > MAX_ACCEL_TRIALS:
+        raise ValueError(f"acceleration_grid: amax / step = {steps:g} (step {step:g} m/s^2) needs more than "
+                         f"{MAX_ACCEL_TRIALS} trials")
+    return step * np.arange(-k, k + 1, dtype=np.float64)
+
+
 # ------------------------------------------------------------------ the device stages
 
 def _series(series, what):
@@ -408,31 +465,48 @@ def periodicity_search(series, sample_time, fmin=None, fmax=None, nharm=16, sigm
     harmonic), ``power`` (the summed normalised power), ``logp`` (``erlang_logsf(power, nharm)``,
     single trial), ``sigma`` (its Gaussian equivalent) and ``nabsorbed``.  ``sift=True`` passes the
     list through :func:`sift_candidates` (``tobs = nfft sample_time``); otherwise ``nabsorbed`` is 0."""
-    from .table import make_table
     nlev = _nlev(nharm)
     x, _, _ = _series(series, "periodicity_search")
     rows, n = x.shape
+    sample_time, nfft, nb, block, thr, kmin, kmax = _search_levels("periodicity_search", n, sample_time, fmin, fmax, nlev,
+                                                                   sigma, block, pad)
+    per = _rows_per_call(rows, nfft)
+    found = [np.zeros(0, _hip.SPEC_CAND_DTYPE)]
+    for r0 in range(0, rows, per):
+        rec = _spectrum_candidates(_rfft_device(x[r0:r0 + per], nfft), nb, block, nlev, thr, kmin, kmax, max_candidates)
+        rec["row"] += r0
+        found.append(rec)
+    return _candidate_table(np.concatenate(found), nfft * sample_time, sift)
+
+
+def _search_levels(what, n, sample_time, fmin, fmax, nlev, sigma, block, pad):
+    """What a search of ``n`` samples fixes before its first batch: (sample_time, nfft, nb, block,
+    and per level the power threshold of ``sigma`` and the bin range of ``[fmin, fmax]``)."""
     nfft = next_nfft(n, pad)
     nb = nfft // 2
     block = _check_block(block, nb)
     sample_time = float(sample_time)
     if not sample_time > 0:
-        raise ValueError("periodicity_search: sample_time must be positive")
+        raise ValueError(f"{what}: sample_time must be positive")
     logp_min = logp_from_sigma(float(sigma))
     thr = np.array([power_threshold(logp_min, 1 << lv) for lv in range(nlev)], np.float32)
     kmin, kmax = bin_ranges(fmin, fmax, nfft, sample_time, nlev, nb)
-    per = _rows_per_call(rows, nfft)
-    found = [np.zeros(0, _hip.SPEC_CAND_DTYPE)]
-    for r0 in range(0, rows, per):
-        part = x[r0:r0 + per]
-        norm = _normalize_device(_rfft_device(part, nfft), nb, block)
-        rec, count = _harmonic_search_device(norm, nlev, thr, kmin, kmax, cap=max(1, int(max_candidates)))
-        if count > rec.size:  # more than the buffer held: once more with room for all
-            rec, count = _harmonic_search_device(norm, nlev, thr, kmin, kmax, cap=count)
-        rec["row"] += r0
-        found.append(rec)
-    rec = np.concatenate(found)
-    tobs = nfft * sample_time
+    return sample_time, nfft, nb, block, thr, kmin, kmax
+
+
+def _spectrum_candidates(spec, nb, block, nlev, thr, kmin, kmax, max_candidates):
+    """The candidate records of a batch of spectra: normalise, sum, pick (``row``: the batch's)."""
+    norm = _normalize_device(spec, nb, block)
+    rec, count = _harmonic_search_device(norm, nlev, thr, kmin, kmax, cap=max(1, int(max_candidates)))
+    if count > rec.size:  # more than the buffer held: once more with room for all
+        rec, count = _harmonic_search_device(norm, nlev, thr, kmin, kmax, cap=count)
+    return rec
+
+
+def _candidate_table(rec, tobs, sift, extra=None):
+    """The table of :func:`periodicity_search` from ``SPEC_CAND_DTYPE`` records (``row`` already
+    the caller's row); ``extra``: further columns, one entry per record."""
+    from .table import make_table
     harm = (1 << rec["level"].astype(np.int64))
     power = rec["power"].astype(np.float64)
     logp = np.zeros(rec.size)
@@ -442,6 +516,7 @@ def periodicity_search(series, sample_time, fmin=None, fmax=None, nharm=16, sigm
     cols = {"freq": rec["bin"].astype(np.float64) / harm / tobs, "row": rec["row"].astype(np.int64), "nharm": harm,
             "bin": rec["bin"].astype(np.int64), "power": rec["power"].astype(np.float32), "logp": logp,
             "sigma": np.array([sigma_from_logp(v) for v in logp], dtype=np.float64)}
+    cols.update(extra or {})
     if sift:
         cols = sift_candidates(cols, tobs)
     else:
@@ -451,5 +526,158 @@ def periodicity_search(series, sample_time, fmin=None, fmax=None, nharm=16, sigm
     return make_table(cols)
 
 
+# ------------------------------------------------------------------ acceleration trials (device)
+
+def _accel_factors(what, accel, sample_time, n, device):
+    """(``af`` as a float64 device tensor (nacc,), ``accel`` was a scalar); ``ValueError`` where the
+    map would stop being monotone (``|af| n > 1``) or ``accel`` is not finite."""
+    t = _hip.torch()
+    acc = np.asarray(accel, dtype=np.float64)
+    scalar = acc.ndim == 0
+    acc = acc.reshape(-1)
+    af = accel_factor(acc, sample_time)
+    if not np.all(np.abs(af) * n <= 1.0):  # (NaN fails too)
+        raise ValueError(f"{what}: |accel| sample_time / (2 c) x {n} samples must be <= 1 and finite: beyond, "
+                         "nearest-neighbour resampling is not monotone")
+    return t.from_numpy(np.ascontiguousarray(af)).to(device), scalar
+
+
+def _resample_device(x, af):
+    """pu_resample_accel of a 2-D row-major device tensor -> (nacc, rows, n) of its dtype."""
+    t = _hip.torch()
+    rows, n = x.shape
+    nacc = af.numel()
+    out = t.empty((nacc, rows, n), dtype=x.dtype, device=x.device)
+    ld = x.stride(0) if rows > 1 else max(x.stride(0), n)
+    _hip.check(_hip.lib().pu_resample_accel(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, ld, _hip.ptr(af), nacc,
+                                            _hip.ptr(out), n, _hip.stream_ptr()), "pu_resample_accel")
+    return out
+
+
+def _accel_batches(rows, nacc, nfft):
+    """The (a0, a1, r0, r1) of the calls that cover nacc x rows (acceleration, row) pairs, sized as
+    :func:`_rows_per_call` sizes rows: whole accelerations per call while ``rows`` fit in one, else
+    one acceleration and the row batches of :func:`periodicity_search`."""
+    per = _rows_per_call(rows * nacc, nfft)
+    if rows <= per:
+        na = per // rows
+        return [(a0, min(a0 + na, nacc), 0, rows) for a0 in range(0, nacc, na)]
+    return [(a, a + 1, r0, min(r0 + per, rows)) for a in range(nacc) for r0 in range(0, rows, per)]
+
+
+def _rfft_accel_device(x, af, mean, nfft, ws, spec=None):
+    """pu_rfft_accel of one batch: ``x`` (rows, n), ``af`` (nacc,), ``mean`` (rows,) -> complex64
+    (nacc * rows, nfft / 2 + 1), pair ``a * rows + r``.  ``ws``: :func:`_aligned` workspace."""
+    t = _hip.torch()
+    rows, n = x.shape
+    nacc = af.numel()
+    if spec is None:
+        spec = t.empty((nacc * rows, nfft // 2 + 1), dtype=t.complex64, device=x.device)
+    ld = x.stride(0) if rows > 1 else max(x.stride(0), n)
+    _hip.check(_hip.lib().pu_rfft_accel(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, ld, _hip.ptr(mean), _hip.ptr(af),
+                                        nacc, nfft, _hip.ptr(spec), spec.stride(0), ws[1], ws[2], _hip.stream_ptr()),
+               "pu_rfft_accel")
+    return spec
+
+
+def _accel_workspace(batches, nfft, device):
+    lib = _hip.lib()
+    return _aligned(max(lib.pu_rfft_accel_workspace_bytes(r1 - r0, a1 - a0, nfft) for a0, a1, r0, r1 in batches), device)
+
+
+def resample(series, accel, sample_time):
+    """``series`` resampled in time at the constant line-of-sight acceleration ``accel`` (m/s^2):
+    sample ``i`` of a row becomes its sample :func:`resample_indices` ``(n, accel_factor(accel,
+    sample_time))[i]``, nearest neighbour.  A scalar ``accel`` gives the series' shape and dtype; an
+    array of ``nacc`` gives ``(nacc, rows, n)`` (``(nacc, n)`` for a 1-D series).  ``ValueError``
+    when ``|accel| sample_time / (2 c) * n > 1``."""
+    x, one_d, as_numpy = _series(series, "resample")
+    af, scalar = _accel_factors("resample", accel, sample_time, x.shape[1], x.device)
+    out = _resample_device(x, af)
+    if one_d:
+        out = out[:, 0]
+    if scalar:
+        out = out[0]
+    return out.cpu().numpy() if as_numpy else out
+
+
+def rfft_accel(series, accels, sample_time, nfft=None):
+    """:func:`rfft` of every row at every trial acceleration, the resampling of :func:`resample`
+    applied where the transform loads its samples (no resampled series is written): complex64
+    ``(nacc, rows, nfft / 2 + 1)`` (``(nacc, nfft / 2 + 1)`` for a 1-D series).  The mean taken out
+    is the row's own (float64 sum / n), the same at every acceleration; with it the result has the
+    bits ``pu_rfft`` gives on the resampled series."""
+    from .stats import _chunk_row_sums
+    t = _hip.torch()
+    x, one_d, as_numpy = _series(series, "rfft_accel")
+    rows, n = x.shape
+    nfft = _check_nfft(nfft, n)
+    af, _ = _accel_factors("rfft_accel", accels, sample_time, n, x.device)
+    nacc = af.numel()
+    spec = t.empty((nacc, rows, nfft // 2 + 1), dtype=t.complex64, device=x.device)
+    if nacc:
+        mean = _chunk_row_sums(x, 3) / float(n)
+        batches = _accel_batches(rows, nacc, nfft)
+        ws = _accel_workspace(batches, nfft, x.device)
+        for a0, a1, r0, r1 in batches:
+            if r1 - r0 == rows:
+                _rfft_accel_device(x, af[a0:a1], mean, nfft, ws, spec=spec[a0:a1].view(-1, nfft // 2 + 1))
+            else:
+                _rfft_accel_device(x[r0:r1], af[a0:a1], mean[r0:r1], nfft, ws, spec=spec[a0, r0:r1])
+    if one_d:
+        spec = spec[:, 0]
+    return spec.cpu().numpy() if as_numpy else spec
+
+
+def acceleration_search(series, sample_time, accels=None, amax=None, fmin=None, fmax=None, nharm=16, sigma=6.0,
+                        block=128, pad=1, sift=True, max_candidates=4096):
+    """:func:`periodicity_search` with an acceleration axis: every row is searched at every trial
+    acceleration, so a pulsar whose frequency drifts across Fourier bins (a binary) adds up again
+    at the trial nearest to its line-of-sight acceleration.
+
+    Give exactly one of ``accels`` (m/s^2, any order) and ``amax``: the latter searches
+    :func:`acceleration_grid` ``(amax, n sample_time, ftop)`` with ``ftop = min(fmax nharm,
+    Nyquist)`` (Nyquist when ``fmax`` is None).  The (acceleration, row) pairs go through
+    ``pu_rfft_accel`` - :func:`rfft_accel`: the resampling happens in the transform's first load,
+    no resampled plane is written - and then through :func:`periodicity_search`'s normalisation,
+    harmonic sums and candidate rule, in batches of at most 1 GiB of FFT workspace.
+
+    Returns :func:`periodicity_search`'s table plus ``accel`` (m/s^2, the trial's); ``row`` is the
+    series' row.  ``sift=True``: :func:`sift_candidates` as there - it merges across rows, so a
+    signal seen at neighbouring accelerations is absorbed into its best one.  ``accels=[0.0]``
+    gives :func:`periodicity_search`'s table.  A constant acceleration only: no jerk."""
+    from .stats import _chunk_row_sums
+    if (accels is None) == (amax is None):
+        raise ValueError("acceleration_search: give exactly one of accels and amax")
+    nlev = _nlev(nharm)
+    x, _, _ = _series(series, "acceleration_search")
+    rows, n = x.shape
+    sample_time, nfft, nb, block, thr, kmin, kmax = _search_levels("acceleration_search", n, sample_time, fmin, fmax, nlev,
+                                                                   sigma, block, pad)
+    if accels is None:
+        nyquist = 0.5 / sample_time
+        ftop = nyquist if fmax is None else min(float(fmax) * int(nharm), nyquist)
+        accels = acceleration_grid(amax, n * sample_time, ftop)
+    accels = np.asarray(accels, dtype=np.float64).reshape(-1)
+    af, _ = _accel_factors("acceleration_search", accels, sample_time, n, x.device)
+    found, found_a = [np.zeros(0, _hip.SPEC_CAND_DTYPE)], [np.zeros(0, np.int64)]
+    if accels.size:
+        means = {}  # per row batch, as periodicity_search takes them
+        batches = _accel_batches(rows, accels.size, nfft)
+        ws = _accel_workspace(batches, nfft, x.device)
+        for a0, a1, r0, r1 in batches:
+            if (r0, r1) not in means:
+                means[r0, r1] = _chunk_row_sums(x[r0:r1], 3) / float(n)
+            spec = _rfft_accel_device(x[r0:r1], af[a0:a1], means[r0, r1], nfft, ws)
+            rec = _spectrum_candidates(spec, nb, block, nlev, thr, kmin, kmax, max_candidates)
+            pair = rec["row"].astype(np.int64)
+            found_a.append(a0 + pair // (r1 - r0))
+            rec["row"] = r0 + pair % (r1 - r0)
+            found.append(rec)
+    return _candidate_table(np.concatenate(found), nfft * sample_time, sift,
+                            extra={"accel": accels[np.concatenate(found_a)] if accels.size else np.zeros(0)})
+
+
 __all__ = ["next_nfft", "harmonic_bins", "erlang_logsf", "power_threshold", "sigma_from_logp", "logp_from_sigma",
-           "bin_ranges", "sift_candidates", "rfft", "power_spectrum", "harmonic_sums", "periodicity_search"]
+           "bin_ranges", "sift_candidates", "rfft", "power_spectrum", "harmonic_sums", "periodicity_search",
+           "accel_factor", "resample_indices", "acceleration_grid", "resample", "rfft_accel", "acceleration_search"]
