@@ -296,13 +296,11 @@ int pu_col_means(const void *x, int dtype, int64_t nrows, int64_t n, int64_t ld,
     PU_REQUIRE(x && out, "pu_col_means: NULL pointer");
     PU_REQUIRE(nrows > 0 && n > 0 && ld >= n, "pu_col_means: bad shape");
     hipStream_t s = pu::as_stream(stream);
-    switch (dtype) {
-    case PU_U8: col_means_t<uint8_t>(x, nrows, n, ld, skip, out, s); break;
-    case PU_F32: col_means_t<float>(x, nrows, n, ld, skip, out, s); break;
-    case PU_F64: col_means_t<double>(x, nrows, n, ld, skip, out, s); break;
-    default: pu::set_error("pu_col_means: unsupported dtype %d", dtype); return PU_EUNSUPPORTED;
-    }
-    return pu::launch_check("colmean_kernel");
+    // (one check after the launches of every column range)
+    int rc = pu::with_dtype<uint8_t, float, double>("pu_col_means", dtype, [&](auto tag) {
+        return col_means_t<typename decltype(tag)::type>(x, nrows, n, ld, skip, out, s);
+    });
+    return rc ? rc : pu::launch_check("colmean_kernel");
 }
 
 static int renorm_apply_any(const void *x, int dtype, int64_t nchan, int64_t n, int64_t ld, const double *factor,
@@ -312,14 +310,12 @@ static int renorm_apply_any(const void *x, int dtype, int64_t nchan, int64_t n, 
     PU_REQUIRE(x && factor && spec && out, "pu_renorm_apply: NULL pointer");
     PU_REQUIRE(nchan > 0 && n > 0 && ld >= n && ld_out >= n, "pu_renorm_apply: bad shape");
     hipStream_t s = pu::as_stream(stream);
-    const int64_t g = ngood_zdm;
-    switch (dtype) {
-    case PU_U8: renorm_apply_t<uint8_t>(x, nchan, n, ld, factor, spec, bad, out, ld_out, col_means, g, s); break;
-    case PU_F32: renorm_apply_t<float>(x, nchan, n, ld, factor, spec, bad, out, ld_out, col_means, g, s); break;
-    case PU_F64: renorm_apply_t<double>(x, nchan, n, ld, factor, spec, bad, out, ld_out, col_means, g, s); break;
-    default: pu::set_error("pu_renorm_apply: unsupported dtype %d", dtype); return PU_EUNSUPPORTED;
-    }
-    return pu::launch_check("apply_kernel");
+    // (one check after the launches of every column range)
+    int rc = pu::with_dtype<uint8_t, float, double>("pu_renorm_apply", dtype, [&](auto tag) {
+        return renorm_apply_t<typename decltype(tag)::type>(x, nchan, n, ld, factor, spec, bad, out, ld_out, col_means,
+                                                            ngood_zdm, s);
+    });
+    return rc ? rc : pu::launch_check("apply_kernel");
 }
 
 int pu_renorm_apply(const void *x, int dtype, int64_t nchan, int64_t n, int64_t ld, const double *factor,
@@ -344,9 +340,8 @@ int pu_zero_columns(double *out, int64_t nrows, int64_t ld, const int64_t *cols,
     if (ncols <= 0) return PU_OK;
     PU_REQUIRE(cols != nullptr, "pu_zero_columns: cols is NULL");
     const unsigned gy = (unsigned)(nrows < 1024 ? nrows : 1024);
-    hipLaunchKernelGGL(zero_cols_kernel, dim3(blocks_for(ncols, 256), gy), dim3(256), 0, pu::as_stream(stream), out,
-                       nrows, ld, cols, ncols);
-    return pu::launch_check("zero_cols_kernel");
+    return pu::launch("zero_cols_kernel", zero_cols_kernel, dim3(blocks_for(ncols, 256), gy), dim3(256), 0,
+                      pu::as_stream(stream), out, nrows, ld, cols, ncols);
 }
 
 }  // extern "C"

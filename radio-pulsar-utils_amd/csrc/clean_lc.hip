@@ -783,19 +783,18 @@ int pu_gaussian_filter1d(const double *x, int64_t n, const double *w, int64_t r,
     if (r <= kGaussMaxR) {
         constexpr int T = kGaussQuadThreads;  // 4 outputs per thread
         const size_t lds = (size_t)(((r + 2) & ~int64_t(1)) + 4 * T + 2 * r + 2 * kGaussPad) * sizeof(double);
-        hipLaunchKernelGGL(gauss_quad_kernel, dim3(blocks_for(n, 4 * T)), dim3(T), lds, pu::as_stream(stream), x, n,
-                           w, (int)r, out);
-        return pu::launch_check("gauss_quad_kernel");
+        return pu::launch("gauss_quad_kernel", gauss_quad_kernel, dim3(blocks_for(n, 4 * T)), dim3(T), lds,
+                          pu::as_stream(stream), x, n, w, (int)r, out);
     }
-    hipLaunchKernelGGL(gauss_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, pu::as_stream(stream), x, n, w, r, out);
-    return pu::launch_check("gauss_kernel");
+    return pu::launch("gauss_kernel", gauss_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, pu::as_stream(stream), x, n, w,
+                      r, out);
 }
 
 int pu_ratio(double num, const double *x, int64_t n, double *out, void *stream)
 {
     PU_REQUIRE(x && out && n > 0, "pu_ratio: bad arguments");
-    hipLaunchKernelGGL(ratio_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, pu::as_stream(stream), num, x, n, out);
-    return pu::launch_check("ratio_kernel");
+    return pu::launch("ratio_kernel", ratio_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, pu::as_stream(stream), num, x,
+                      n, out);
 }
 
 size_t pu_cut_outliers_workspace_bytes(int64_t n)
@@ -834,8 +833,7 @@ int cut_outliers(const double *lc, int64_t n, double *out, int64_t nrows, int64_
                  size_t ws_bytes, void *stream, bool exact_only)
 {
     PU_REQUIRE(lc && out && mask && n >= 64 && nrows > 0 && ld_out >= n, "pu_cut_outliers: bad arguments");
-    PU_REQUIRE(ws && ws_bytes >= pu_cut_outliers_workspace_bytes(n) && reinterpret_cast<uintptr_t>(ws) % 8 == 0,
-               "pu_cut_outliers: workspace too small or not 8-byte aligned");
+    if (int rc = pu::check_workspace("pu_cut_outliers", ws, ws_bytes, pu_cut_outliers_workspace_bytes(n), 8)) return rc;
     hipStream_t s = pu::as_stream(stream);
     OutlierState *st = reinterpret_cast<OutlierState *>(ws);
     double *u = reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + 256);
@@ -864,8 +862,7 @@ int cut_outliers(const double *lc, int64_t n, double *out, int64_t nrows, int64_
             static std::atomic<uint64_t> attr_set{0};  // per device: 64 KB static (the exact
                                                       // path's staging) + the window means
             if (dev < 64 && !(attr_set.load() >> dev & 1)) {
-                PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(outlier_fused_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 1024 * (int)sizeof(double)));
+                if (int rc = pu::raise_lds(outlier_fused_kernel, 8 * 1024 * sizeof(double))) return rc;
                 attr_set.fetch_or(uint64_t(1) << dev);
             }
             // resident workgroups per CU at this LDS size (cached per device and size)
@@ -881,9 +878,10 @@ int cut_outliers(const double *lc, int64_t n, double *out, int64_t nrows, int64_
         if (resident) {
             PU_TRY_HIP(hipMemsetAsync(st, 0, 128, s));
             OutlierBar *ob = reinterpret_cast<OutlierBar *>(reinterpret_cast<char *>(ws) + 64);
-            hipLaunchKernelGGL(outlier_fused_kernel, dim3(grid), dim3(256), (size_t)segs * 1024 * sizeof(double), s, lc,
-                               n, st, ob, u, u16, mask, list, out, nrows, ld_out, segs);
-            return pu::launch_check("outlier_fused_kernel");
+            // (at most the 64 KiB raised above: pu::launch raises nothing here)
+            return pu::launch("outlier_fused_kernel", outlier_fused_kernel, dim3(grid), dim3(256),
+                              (size_t)segs * 1024 * sizeof(double), s, lc, n, st, ob, u, u16, mask, list, out, nrows, ld_out,
+                              segs);
         }
     }
     PU_TRY_HIP(hipMemsetAsync(st, 0, 64, s));
@@ -917,8 +915,7 @@ size_t pu_median_workspace_bytes(void) { return sizeof(MedState) + kMedBufs * 2 
 int pu_median(const double *x, int64_t n, double *out, void *ws, size_t ws_bytes, void *stream)
 {
     PU_REQUIRE(x && out && n > 0, "pu_median: bad arguments");
-    PU_REQUIRE(ws && ws_bytes >= pu_median_workspace_bytes(), "pu_median: workspace too small");
-    PU_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, "pu_median: workspace not 8-byte aligned");
+    if (int rc = pu::check_workspace("pu_median", ws, ws_bytes, pu_median_workspace_bytes(), 8)) return rc;
     hipStream_t s = pu::as_stream(stream);
     MedState *st = reinterpret_cast<MedState *>(ws);
     uint32_t *hist = reinterpret_cast<uint32_t *>(st + 1);
@@ -935,32 +932,43 @@ int pu_median(const double *x, int64_t n, double *out, void *ws, size_t ws_bytes
 int pu_ratio_dev(const double *numerator, const double *x, int64_t n, double *out, void *stream)
 {
     PU_REQUIRE(numerator && x && out && n > 0, "pu_ratio_dev: bad arguments");
-    hipLaunchKernelGGL(ratio_dev_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, pu::as_stream(stream), numerator, x,
-                       n, out);
-    return pu::launch_check("ratio_dev_kernel");
+    return pu::launch("ratio_dev_kernel", ratio_dev_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, pu::as_stream(stream),
+                      numerator, x, n, out);
 }
 
-size_t pu_lc_factor_workspace_bytes(int64_t n)
+namespace {
+// pu_lc_factor's workspace: the smoothed series, pu_median's workspace and the median
+struct LcFactorWs {
+    double *smooth, *med;
+    void *mws;
+    size_t bytes;
+};
+
+LcFactorWs lc_factor_carve(pu::Carver c, int64_t n)
 {
-    // the smoothed series, pu_median's workspace and the median
-    return (((size_t)std::max<int64_t>(n, 0) * 8 + 255) & ~size_t(255)) + pu_median_workspace_bytes() + 64;
+    LcFactorWs w;
+    w.smooth = c.take<double>((size_t)std::max<int64_t>(n, 0) * 8);
+    w.mws = c.take<char>(pu_median_workspace_bytes());
+    w.med = c.take<double>(64, 8);
+    w.bytes = c.used();
+    return w;
 }
+}  // namespace
+
+size_t pu_lc_factor_workspace_bytes(int64_t n) { return lc_factor_carve(pu::Carver(), n).bytes; }
 
 int pu_lc_factor(const double *lc, int64_t n, const double *w, int64_t r, double *factor, double *median_out, void *ws,
                  size_t ws_bytes, void *stream)
 {
     PU_REQUIRE(lc && w && factor && n > 0 && r >= 0, "pu_lc_factor: bad arguments");
-    PU_REQUIRE(ws && ws_bytes >= pu_lc_factor_workspace_bytes(n) && reinterpret_cast<uintptr_t>(ws) % 256 == 0,
-               "pu_lc_factor: workspace too small or not 256-byte aligned");
-    char *wsb = reinterpret_cast<char *>(ws);
+    const LcFactorWs p = lc_factor_carve(pu::Carver(ws), n);
+    if (int rc = pu::check_workspace("pu_lc_factor", ws, ws_bytes, p.bytes, 256)) return rc;
     // Gaussian, median, ratio, launch by launch (a one-launch form with grid barriers measured
     // slower: see the grid-barrier note above)
-    double *smooth = reinterpret_cast<double *>(wsb);
-    char *mws = wsb + (((size_t)n * 8 + 255) & ~size_t(255));
-    double *med = reinterpret_cast<double *>(mws + pu_median_workspace_bytes());
-    int rc = pu_gaussian_filter1d(lc, n, w, r, smooth, stream);
-    if (!rc) rc = pu_median(smooth, n, median_out ? median_out : med, mws, pu_median_workspace_bytes(), stream);
-    if (!rc) rc = pu_ratio_dev(median_out ? median_out : med, smooth, n, factor, stream);
+    double *med = median_out ? median_out : p.med;
+    int rc = pu_gaussian_filter1d(lc, n, w, r, p.smooth, stream);
+    if (!rc) rc = pu_median(p.smooth, n, med, p.mws, pu_median_workspace_bytes(), stream);
+    if (!rc) rc = pu_ratio_dev(med, p.smooth, n, factor, stream);
     return rc;
 }
 

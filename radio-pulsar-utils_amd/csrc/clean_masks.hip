@@ -458,15 +458,12 @@ int pu_variability_cert(const void *means, int dtype, const double *moments, int
                (long long)nrows, kNoisyMax);
     PU_REQUIRE(n >= 1, "pu_variability_cert: n must be positive");
     PU_REQUIRE(dtype == PU_F32 || dtype == PU_F64, "pu_variability_cert: means must be float32 or float64");
-    if (dtype == PU_F32)
-        hipLaunchKernelGGL(variability_cert_kernel<float>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
-                           reinterpret_cast<const float *>(means), moments, (int)nrows, (double)n, mef, gam, u, bad,
-                           mask, flag);
-    else
-        hipLaunchKernelGGL(variability_cert_kernel<double>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
-                           reinterpret_cast<const double *>(means), moments, (int)nrows, (double)n, mef, gam, u, bad,
-                           mask, flag);
-    return pu::launch_check("variability_cert_kernel");
+    return pu::with_dtype<float, double>("pu_variability_cert", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return pu::launch("variability_cert_kernel", variability_cert_kernel<T>, dim3(1), dim3(1024), 0,
+                          pu::as_stream(stream), reinterpret_cast<const T *>(means), moments, (int)nrows, (double)n, mef,
+                          gam, u, bad, mask, flag);
+    });
 }
 
 int pu_noisy_channels(const void *spec, int dtype, int64_t n, double mad_c, uint8_t *mask, int32_t *flag,
@@ -475,13 +472,11 @@ int pu_noisy_channels(const void *spec, int dtype, int64_t n, double mad_c, uint
     PU_REQUIRE(spec && mask && flag, "pu_noisy_channels: NULL pointer");
     PU_REQUIRE(n >= 2 && n <= kNoisyMax, "pu_noisy_channels: n = %lld outside [2, %d]", (long long)n, kNoisyMax);
     PU_REQUIRE(dtype == PU_F32 || dtype == PU_F64, "pu_noisy_channels: spec must be float32 or float64");
-    if (dtype == PU_F32)
-        hipLaunchKernelGGL(noisy_channels_kernel<float>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
-                           reinterpret_cast<const float *>(spec), (int)n, mad_c, mask, flag);
-    else
-        hipLaunchKernelGGL(noisy_channels_kernel<double>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
-                           reinterpret_cast<const double *>(spec), (int)n, mad_c, mask, flag);
-    return pu::launch_check("noisy_channels_kernel");
+    return pu::with_dtype<float, double>("pu_noisy_channels", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return pu::launch("noisy_channels_kernel", noisy_channels_kernel<T>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
+                          reinterpret_cast<const T *>(spec), (int)n, mad_c, mask, flag);
+    });
 }
 
 int pu_channel_masks(const void *means, int dtype, const double *moments, int64_t nrows, int64_t n, double mad_c,
@@ -493,15 +488,12 @@ int pu_channel_masks(const void *means, int dtype, const double *moments, int64_
                kMasksMax);
     PU_REQUIRE(n >= 1, "pu_channel_masks: n must be positive");
     PU_REQUIRE(dtype == PU_F32 || dtype == PU_F64, "pu_channel_masks: means must be float32 or float64");
-    if (dtype == PU_F32)
-        hipLaunchKernelGGL(channel_masks_kernel<float>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
-                           reinterpret_cast<const float *>(means), moments, (int)nrows, mad_c, (double)n, mef, gam, u,
-                           noisy, noisy_flag, var, var_flag);
-    else
-        hipLaunchKernelGGL(channel_masks_kernel<double>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
-                           reinterpret_cast<const double *>(means), moments, (int)nrows, mad_c, (double)n, mef, gam,
-                           u, noisy, noisy_flag, var, var_flag);
-    return pu::launch_check("channel_masks_kernel");
+    return pu::with_dtype<float, double>("pu_channel_masks", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return pu::launch("channel_masks_kernel", channel_masks_kernel<T>, dim3(1), dim3(1024), 0, pu::as_stream(stream),
+                          reinterpret_cast<const T *>(means), moments, (int)nrows, mad_c, (double)n, mef, gam, u, noisy,
+                          noisy_flag, var, var_flag);
+    });
 }
 
 }  // extern "C"

@@ -265,28 +265,43 @@ int row_sums_t(const void *x, int64_t nrows, int64_t n, int64_t ld, const void *
         if (rc) return rc;
     }
     if (tail) {
-        hipLaunchKernelGGL((rowsum_tail_kernel<Tin, Ta, MODE>), dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, s,
-                           xp, ld, nrows, n, nfull, nblk_row, cp, scale, bs);
-        int rc = pu::launch_check("rowsum_tail_kernel");
+        int rc = pu::launch("rowsum_tail_kernel", rowsum_tail_kernel<Tin, Ta, MODE>, dim3((unsigned)((nrows + 63) / 64)),
+                            dim3(64), 0, s, xp, ld, nrows, n, nfull, nblk_row, cp, scale, bs, nullptr);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL((rowsum_combine<Ta>), dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, bs, nrows,
-                       nblk_row, divisor, reinterpret_cast<Ta *>(out));
-    return pu::launch_check("rowsum_combine");
+    return pu::launch("rowsum_combine", rowsum_combine<Ta>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, bs,
+                      nrows, nblk_row, divisor, reinterpret_cast<Ta *>(out));
+}
+
+// pu_row_moments' workspace: a sum per block (of rows x blocks per row), then 2 doubles per block
+struct MomentsWs {
+    void *bs;
+    double *mb;
+    size_t bytes;
+};
+
+MomentsWs moments_carve(pu::Carver c, int64_t nrows, int64_t n)
+{
+    const int64_t nblk = (n + kBlock - 1) / kBlock;
+    const size_t nb = (size_t)(nrows > 0 ? nrows : 0) * (size_t)(nblk > 0 ? nblk : 1);
+    MomentsWs w;
+    w.bs = c.take<char>(nb * sizeof(double), 8);
+    w.mb = c.take<double>(nb * 2 * sizeof(double));
+    w.bytes = c.used();
+    return w;
 }
 
 // numpy's row means (MODE 0 order, divided by n) and, in the same pass, the shifted
-// moments of every row (pu_row_moments).  ws: the block sums, then 2 doubles per block.
+// moments of every row (pu_row_moments).
 template <typename Tin, typename Ta>
-int row_moments_t(const void *x, int64_t nrows, int64_t n, int64_t ld, void *means, double *moments, void *ws,
-                  hipStream_t s)
+int row_moments_t(const void *x, int64_t nrows, int64_t n, int64_t ld, void *means, double *moments,
+                  const MomentsWs &w, hipStream_t s)
 {
     const int64_t nfull = n / kBlock;
     const int64_t tail = n % kBlock;
     const int64_t nblk_row = nfull + (tail ? 1 : 0);
-    Ta *bs = reinterpret_cast<Ta *>(ws);
-    double *mb = reinterpret_cast<double *>(reinterpret_cast<char *>(ws) +
-                                            (((size_t)nrows * nblk_row * sizeof(double) + 255) & ~size_t(255)));
+    Ta *bs = reinterpret_cast<Ta *>(w.bs);
+    double *mb = w.mb;
     const Tin *xp = reinterpret_cast<const Tin *>(x);
     if (nfull > 0) {
         PU_REQUIRE(nrows * nfull < (int64_t(1) << 31), "pu_row_moments: too many blocks");
@@ -301,14 +316,12 @@ int row_moments_t(const void *x, int64_t nrows, int64_t n, int64_t ld, void *mea
         if (rc) return rc;
     }
     if (tail) {
-        hipLaunchKernelGGL((rowsum_tail_kernel<Tin, Ta, 0, true>), dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0,
-                           s, xp, ld, nrows, n, nfull, nblk_row, nullptr, nullptr, bs, mb);
-        int rc = pu::launch_check("rowsum_tail_kernel");
+        int rc = pu::launch("rowsum_tail_kernel", rowsum_tail_kernel<Tin, Ta, 0, true>, dim3((unsigned)((nrows + 63) / 64)),
+                            dim3(64), 0, s, xp, ld, nrows, n, nfull, nblk_row, nullptr, nullptr, bs, mb);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL((row_moments_combine<Tin, Ta>), dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, bs, mb,
-                       xp, ld, nrows, nblk_row, (double)n, reinterpret_cast<Ta *>(means), moments);
-    return pu::launch_check("row_moments_combine");
+    return pu::launch("row_moments_combine", row_moments_combine<Tin, Ta>, dim3((unsigned)((nrows + 255) / 256)), dim3(256),
+                      0, s, bs, mb, xp, ld, nrows, nblk_row, (double)n, reinterpret_cast<Ta *>(means), moments);
 }
 
 template <typename Tin>
@@ -344,22 +357,18 @@ int pu_row_sums(const void *x, int dtype, int64_t nrows, int64_t n, int64_t ld, 
     PU_REQUIRE(mode >= 0 && mode <= 4, "pu_row_sums: bad mode %d", mode);
     PU_REQUIRE(mode != 1 || center, "pu_row_sums: mode 1 needs center");
     PU_REQUIRE(mode != 2 || scale, "pu_row_sums: mode 2 needs scale");
-    PU_REQUIRE(ws && ws_bytes >= pu_row_sums_workspace_bytes(nrows, n), "pu_row_sums: workspace too small");
+    if (int rc = pu::check_workspace("pu_row_sums", ws, ws_bytes, pu_row_sums_workspace_bytes(nrows, n), 1)) return rc;
     hipStream_t s = pu::as_stream(stream);
-    switch (dtype) {
-    case PU_U8: return row_sums_in<uint8_t>(mode, false, x, nrows, n, ld, center, scale, divisor, out, ws, s);
-    case PU_F32: return row_sums_in<float>(mode, true, x, nrows, n, ld, center, scale, divisor, out, ws, s);
-    case PU_F64: return row_sums_in<double>(mode, false, x, nrows, n, ld, center, scale, divisor, out, ws, s);
-    }
-    pu::set_error("pu_row_sums: unsupported dtype %d", dtype);
-    return PU_EUNSUPPORTED;
+    return pu::with_dtype<uint8_t, float, double>("pu_row_sums", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        // float32 input accumulates in float32 (modes 0 and 1)
+        return row_sums_in<T>(mode, std::is_same_v<T, float>, x, nrows, n, ld, center, scale, divisor, out, ws, s);
+    });
 }
 
 size_t pu_row_moments_workspace_bytes(int64_t nrows, int64_t n)
 {
-    const int64_t nblk = (n + kBlock - 1) / kBlock;
-    const size_t nb = (size_t)(nrows > 0 ? nrows : 0) * (size_t)(nblk > 0 ? nblk : 1);
-    return ((nb * sizeof(double) + 255) & ~size_t(255)) + nb * 2 * sizeof(double);
+    return moments_carve(pu::Carver(), nrows, n).bytes;
 }
 
 int pu_row_moments(const void *x, int dtype, int64_t nrows, int64_t n, int64_t ld, void *means, double *moments,
@@ -367,16 +376,15 @@ int pu_row_moments(const void *x, int dtype, int64_t nrows, int64_t n, int64_t l
 {
     PU_REQUIRE(x && means && moments, "pu_row_moments: NULL pointer");
     PU_REQUIRE(nrows > 0 && n > 0 && ld >= n, "pu_row_moments: bad shape");
-    PU_REQUIRE(ws && ws_bytes >= pu_row_moments_workspace_bytes(nrows, n) && reinterpret_cast<uintptr_t>(ws) % 8 == 0,
-               "pu_row_moments: workspace too small or not 8-byte aligned");
+    const MomentsWs w = moments_carve(pu::Carver(ws), nrows, n);
+    if (int rc = pu::check_workspace("pu_row_moments", ws, ws_bytes, w.bytes, 8)) return rc;
     hipStream_t s = pu::as_stream(stream);
-    switch (dtype) {
-    case PU_U8: return row_moments_t<uint8_t, double>(x, nrows, n, ld, means, moments, ws, s);
-    case PU_F32: return row_moments_t<float, float>(x, nrows, n, ld, means, moments, ws, s);
-    case PU_F64: return row_moments_t<double, double>(x, nrows, n, ld, means, moments, ws, s);
-    }
-    pu::set_error("pu_row_moments: unsupported dtype %d", dtype);
-    return PU_EUNSUPPORTED;
+    return pu::with_dtype<uint8_t, float, double>("pu_row_moments", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        // the accumulator: float32 for float32 input, float64 otherwise
+        using Ta = std::conditional_t<std::is_same_v<T, float>, float, double>;
+        return row_moments_t<T, Ta>(x, nrows, n, ld, means, moments, w, s);
+    });
 }
 
 }  // extern "C"

@@ -326,12 +326,7 @@ int launch(bool plane, const DedispArgs &a, size_t lds_bytes, const int32_t *fir
 {
     const dim3 grid((unsigned)((int64_t)a.ndt * a.ntt_run)), block(64 * kF64W);
     auto go = [&](auto kern) {
-        if (lds_bytes > 64 * 1024) {
-            int rc = pu::hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes),
-                                   "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            if (rc) return rc;
-        }
+        if (int rc = pu::ensure_lds(kern, lds_bytes)) return rc;
         hipLaunchKernelGGL(kern, grid, block, lds_bytes, s, a, first, count, rowlen, base, rec, first_off);
         return pu::launch_check("dedisp_f64_kernel");
     };

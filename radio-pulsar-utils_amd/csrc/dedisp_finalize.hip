@@ -267,10 +267,20 @@ int pu_dd_resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, 
     const int64_t n = p->pb.n, nchan = p->pb.nchan;
     const int64_t per_row = n * 8 + (int64_t)pu_series_stats_workspace_bytes(1, n) + nchan * 8;
     const int64_t B = std::max<int64_t>(1, std::min<int64_t>(nflag, (int64_t(1) << 30) / per_row));
-    const size_t plane_b = ((size_t)B * n * sizeof(double) + 255) & ~size_t(255);
-    const size_t sws_b = (pu_series_stats_workspace_bytes(B, n) + 255) & ~size_t(255);
-    const size_t sh_b = ((size_t)B * nchan * sizeof(int64_t) + 255) & ~size_t(255);
-    const size_t need = plane_b + sws_b + sh_b + (size_t)B * sizeof(int32_t);
+    // the scratch of a batch: its series, pu_series_stats' workspace, its shifts and trial numbers
+    const size_t sws_b = pu_series_stats_workspace_bytes(B, n);
+    double *plane = nullptr;
+    void *sws = nullptr;
+    int64_t *d_sh = nullptr;
+    int32_t *d_idx = nullptr;
+    auto carve = [&](pu::Carver c) {
+        plane = c.take<double>((size_t)B * n * sizeof(double));
+        sws = c.take<char>(sws_b);
+        d_sh = c.take<int64_t>((size_t)B * nchan * sizeof(int64_t));
+        d_idx = c.take<int32_t>((size_t)B * sizeof(int32_t));
+        return c.used();
+    };
+    const size_t need = carve(pu::Carver());
     // per-call scratch, stream-ordered (no device-wide synchronisation, nothing held
     // with the plan between calls); freed on every return path
     void *rc_buf = nullptr;
@@ -284,11 +294,7 @@ int pu_dd_resolve_flagged(pu_plan *p, const void *data, int64_t ld, double *mx, 
             (void)hipStreamSynchronize(s);
         }
     } scratch{rc_buf, s};
-    char *sc = reinterpret_cast<char *>(rc_buf);
-    double *plane = reinterpret_cast<double *>(sc);
-    void *sws = sc + plane_b;
-    int64_t *d_sh = reinterpret_cast<int64_t *>(sc + plane_b + sws_b);
-    int32_t *d_idx = reinterpret_cast<int32_t *>(sc + plane_b + sws_b + sh_b);
+    carve(pu::Carver(rc_buf));
     std::vector<int64_t> sh;
     int rc = PU_OK;
     for (int64_t i0 = 0; !rc && i0 < nflag; i0 += B) {

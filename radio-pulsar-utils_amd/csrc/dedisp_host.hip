@@ -242,7 +242,7 @@ int pu_plan_search_tiles(pu_plan *p, const void *data, int64_t ld, int64_t tt_be
     PU_REQUIRE(0 <= tt_begin && tt_begin <= tt_end && tt_end <= p->t.ntt,
                "pu_plan_search_tiles: tile range [%lld, %lld) outside [0, %d)", (long long)tt_begin,
                (long long)tt_end, p->t.ntt);
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p), "pu_plan_search_tiles: workspace too small");
+    if ((rc = pu::check_workspace("pu_plan_search_tiles", workspace, ws_bytes, pu_plan_workspace_bytes(p), 1))) return rc;
     if (tt_begin == tt_end) return PU_OK;
     DedispArgs a = make_args(p, data, ld);
     a.partials = workspace;
@@ -261,8 +261,7 @@ static int finalize_range(const char *who, pu_plan *p, int64_t begin, int64_t en
     PU_REQUIRE(0 <= begin && begin <= end && end <= p->pb.ndm, "%s: trial range [%lld, %lld) outside [0, %lld)", who,
                (long long)begin, (long long)end, (long long)p->pb.ndm);
     PU_REQUIRE(outputs && max_out && std_out && snr_out && rebin_out, "%s: NULL output", who);
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "%s: workspace too small or not 8-byte aligned", who);
+    if (int rc = pu::check_workspace(who, workspace, ws_bytes, pu_plan_workspace_bytes(p), 8)) return rc;
     char *ws = reinterpret_cast<char *>(workspace);
     return pu_dd_launch_finalize(p, ws, max_out, std_out, snr_out, rebin_out, ws, stream, false, begin, end - begin);
 }
@@ -380,8 +379,7 @@ int pu_plan_search(pu_plan *p, const void *data, int64_t ld, double *max_out, do
     if (rc) return rc;
     std::lock_guard<std::mutex> guard(p->lock);
     PU_REQUIRE(max_out && std_out && snr_out && rebin_out, "pu_plan_search: NULL output");
-    PU_REQUIRE(workspace && ws_bytes >= pu_plan_workspace_bytes(p) && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "pu_plan_search: workspace too small or not 8-byte aligned");
+    if ((rc = pu::check_workspace("pu_plan_search", workspace, ws_bytes, pu_plan_workspace_bytes(p), 8))) return rc;
     DedispArgs a = make_args(p, data, ld);
     a.partials = workspace;
     hipStream_t s = pu::as_stream(stream);

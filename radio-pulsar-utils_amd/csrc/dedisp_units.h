@@ -94,17 +94,7 @@ namespace pu {
 // certification state follows them in the workspace
 static inline size_t part_bytes(const pu_plan *p)
 {
-    return ((size_t)p->pb.ndm * p->t.ntt * kPartStride * part_elem(p->pb) + 255) & ~size_t(255);
-}
-
-// Dynamic LDS above 64 KiB needs the kernel's attribute raised before its launch.
-template <typename Kern>
-int ensure_lds(Kern kern, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return PU_OK;
-    return hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
-                     "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    return up256((size_t)p->pb.ndm * p->t.ntt * kPartStride * part_elem(p->pb));
 }
 
 }  // namespace pu

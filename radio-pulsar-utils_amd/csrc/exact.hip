@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "exact.h"
 #include "pu_common.h"
@@ -333,9 +334,8 @@ struct StatsWs {
     void *rs;
     size_t rs_bytes;
     int64_t *blk, *total;  // events only: per-workgroup run-start counts / offsets, running total
+    size_t bytes;          // of the whole layout
 };
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
 // Workgroups of the event stage per row: one per kEvBlock bins of each window.
 constexpr int kEvPerLane = 8;
@@ -349,52 +349,33 @@ int64_t event_blocks(int64_t n)
     return t;
 }
 
-size_t stats_bytes(int64_t rows, int64_t n)
+// The layout, written once: on a workspace it yields the pieces, on a null base only the
+// size (stats_bytes, events_bytes).
+StatsWs carve(pu::Carver c, int64_t rows, int64_t n, bool events = false)
 {
-    return up256(rows * n * 8) + up256(rows * (n / 2) * 8) + up256(pu_row_sums_workspace_bytes(rows, n)) +
-           up256(rows * 8) + 2 * up256(4 * rows * 8) + up256(4 * rows * 8);
-}
-
-size_t events_bytes(int64_t rows, int64_t n)
-{
-    return stats_bytes(rows, n) + up256(rows * (n / 4) * 8) + up256(rows * (n / 8) * 8) +
-           up256(rows * event_blocks(n) * 8) + 256;
-}
-
-StatsWs carve(void *ws, int64_t rows, int64_t n, bool events = false)
-{
-    char *p = reinterpret_cast<char *>(ws);
     StatsWs w;
-    w.blk = w.total = nullptr;
-    if (events) {  // the running total first: at the same place for every batch size
-        w.total = reinterpret_cast<int64_t *>(p);
-        p += 256;
-    }
-    w.S = reinterpret_cast<double *>(p);
-    p += up256(rows * n * 8);
-    w.R[0] = w.S;
-    w.R[1] = w.R[2] = w.R[3] = reinterpret_cast<double *>(p);
-    p += up256(rows * (n / 2) * 8);
-    w.rs = p;
+    // the running total first: at the same place for every batch size
+    w.total = events ? c.take<int64_t>(sizeof(int64_t)) : nullptr;
+    w.S = w.R[0] = c.take<double>(rows * n * 8);
+    w.R[1] = w.R[2] = w.R[3] = c.take<double>(rows * (n / 2) * 8);
     w.rs_bytes = pu_row_sums_workspace_bytes(rows, n);
-    p += up256(w.rs_bytes);
-    w.mean = reinterpret_cast<double *>(p);
-    p += up256(rows * 8);
-    w.mw = reinterpret_cast<double *>(p);
-    p += up256(4 * rows * 8);
-    w.var = reinterpret_cast<double *>(p);
-    p += up256(4 * rows * 8);
-    w.keys = reinterpret_cast<uint64_t *>(p);
-    p += up256(4 * rows * 8);
+    w.rs = c.take<char>(w.rs_bytes);
+    w.mean = c.take<double>(rows * 8);
+    w.mw = c.take<double>(4 * rows * 8);
+    w.var = c.take<double>(4 * rows * 8);
+    w.keys = c.take<uint64_t>(4 * rows * 8);
+    w.blk = nullptr;
     if (events) {
-        w.R[2] = reinterpret_cast<double *>(p);
-        p += up256(rows * (n / 4) * 8);
-        w.R[3] = reinterpret_cast<double *>(p);
-        p += up256(rows * (n / 8) * 8);
-        w.blk = reinterpret_cast<int64_t *>(p);
+        w.R[2] = c.take<double>(rows * (n / 4) * 8);
+        w.R[3] = c.take<double>(rows * (n / 8) * 8);
+        w.blk = c.take<int64_t>(rows * event_blocks(n) * 8);
     }
+    w.bytes = pu::up256(c.used());  // whole 256-byte pieces
     return w;
 }
+
+size_t stats_bytes(int64_t rows, int64_t n) { return carve(pu::Carver(), rows, n).bytes; }
+size_t events_bytes(int64_t rows, int64_t n) { return carve(pu::Carver(), rows, n, true).bytes; }
 
 // The part pu_series_stats and pu_series_events share: mean, S = row - mean, the rebinned
 // series R[k] (row stride n >> k), the variance of each (numpy's order) and the max keys.
@@ -404,17 +385,17 @@ int stats_moments(const double *plane, int64_t rows, int64_t n, int64_t ld, cons
     int rc = pu_row_sums(plane, PU_F64, rows, n, ld, 0, nullptr, nullptr, (double)n, w.mean, w.rs, w.rs_bytes, s);
     if (rc) return rc;
     PU_TRY_HIP(hipMemsetAsync(w.keys, 0, 4 * rows * sizeof(uint64_t), s));
-    hipLaunchKernelGGL(exact_shift_kernel, dim3(grid_for(n, 64), (unsigned)rows), blk, 0, s, plane, ld, n, w.mean, w.S,
-                       w.keys);
-    if ((rc = pu::launch_check("exact_shift_kernel"))) return rc;
+    rc = pu::launch("exact_shift_kernel", exact_shift_kernel, dim3(grid_for(n, 64), (unsigned)rows), blk, 0, s, plane, ld,
+                    n, w.mean, w.S, w.keys);
+    if (rc) return rc;
     for (int k = 0; k < 4; ++k) {
         const int win = 1 << k;
         const int64_t nb = n / win;
         if (nb == 0) break;
         if (k > 0) {
-            hipLaunchKernelGGL(exact_rebin_kernel, dim3(grid_for(nb, 64), (unsigned)rows), blk, 0, s, w.S, n, win, nb,
-                               w.R[k], w.keys + k * rows);
-            if ((rc = pu::launch_check("exact_rebin_kernel"))) return rc;
+            rc = pu::launch("exact_rebin_kernel", exact_rebin_kernel, dim3(grid_for(nb, 64), (unsigned)rows), blk, 0, s,
+                            w.S, n, win, nb, w.R[k], w.keys + k * rows);
+            if (rc) return rc;
         }
         const double *src = w.R[k];
         // np.std(reb): mean, then the sum of squared deviations, both in numpy's order
@@ -431,12 +412,11 @@ int stats_moments(const double *plane, int64_t rows, int64_t n, int64_t ld, cons
 int stats_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const int32_t *idx, double *max_out,
                 double *std_out, double *snr_out, int32_t *win_out, void *ws, hipStream_t s)
 {
-    StatsWs w = carve(ws, rows, n);
+    StatsWs w = carve(pu::Carver(ws), rows, n);
     int rc = stats_moments(plane, rows, n, ld, w, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(exact_final_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, rows, n, w.keys, w.var,
-                       idx, max_out, std_out, snr_out, win_out);
-    return pu::launch_check("exact_final_kernel");
+    return pu::launch("exact_final_kernel", exact_final_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, rows,
+                      n, w.keys, w.var, idx, max_out, std_out, snr_out, win_out);
 }
 
 // ---- events (pu_series_events; the definitions are in pulsarutils_hip.h) ----
@@ -583,7 +563,7 @@ event_emit_kernel(const double *__restrict__ R, int64_t nb, int window, const do
 int events_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const int32_t *idx, int64_t row0,
                  double thr, pu_event *events, int64_t cap, void *ws, hipStream_t s)
 {
-    StatsWs w = carve(ws, rows, n, true);
+    StatsWs w = carve(pu::Carver(ws), rows, n, true);
     int rc = stats_moments(plane, rows, n, ld, w, s);
     if (rc) return rc;
     const int64_t per_row = event_blocks(n);
@@ -595,17 +575,17 @@ int events_batch(const double *plane, int64_t rows, int64_t n, int64_t ld, const
         f += nblk[k];
     }
     for (int k = 0; k < 4 && nblk[k]; ++k) {
-        hipLaunchKernelGGL(event_count_kernel, dim3((unsigned)nblk[k], (unsigned)rows), dim3(256), 0, s, w.R[k], n >> k,
-                           w.var + k * rows, thr, w.blk, per_row, first[k]);
-        if ((rc = pu::launch_check("event_count_kernel"))) return rc;
+        rc = pu::launch("event_count_kernel", event_count_kernel, dim3((unsigned)nblk[k], (unsigned)rows), dim3(256), 0, s,
+                        w.R[k], n >> k, w.var + k * rows, thr, w.blk, per_row, first[k]);
+        if (rc) return rc;
     }
-    hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(1024), 0, s, w.blk, rows * per_row, w.total);
-    if ((rc = pu::launch_check("event_scan_kernel"))) return rc;
+    rc = pu::launch("event_scan_kernel", event_scan_kernel, dim3(1), dim3(1024), 0, s, w.blk, rows * per_row, w.total);
+    if (rc) return rc;
     if (cap == 0) return PU_OK;
     for (int k = 0; k < 4 && nblk[k]; ++k) {
-        hipLaunchKernelGGL(event_emit_kernel, dim3((unsigned)nblk[k], (unsigned)rows), dim3(256), 0, s, w.R[k], n >> k,
-                           1 << k, w.var + k * rows, thr, w.blk, per_row, first[k], idx, row0, events, cap);
-        if ((rc = pu::launch_check("event_emit_kernel"))) return rc;
+        rc = pu::launch("event_emit_kernel", event_emit_kernel, dim3((unsigned)nblk[k], (unsigned)rows), dim3(256), 0, s,
+                        w.R[k], n >> k, 1 << k, w.var + k * rows, thr, w.blk, per_row, first[k], idx, row0, events, cap);
+        if (rc) return rc;
     }
     return PU_OK;
 }
@@ -636,37 +616,27 @@ int exact_series(const void *data, int dtype, int64_t nchan, int64_t n, int64_t 
     if (t_len < 0) t_len = n - t_begin;
     if (t_len <= 0 || rows <= 0) return PU_OK;
     const dim3 grid((unsigned)((t_len + 4 * 64 * kSeriesPer - 1) / (4 * 64 * kSeriesPer)), (unsigned)rows), blk(256);
-    switch (dtype) {
-    case PU_U8:
-        if ((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (ld & 3) == 0) {
-            // integer channel segments, float64 atomics (exact: integer sums < 2^53)
-            PU_TRY_HIP(hipMemsetAsync(out, 0, (size_t)rows * (size_t)t_len * sizeof(double), s));
-            const dim3 g3(grid.x, grid.y, (unsigned)((nchan + kSegChans - 1) / kSegChans));
-            hipLaunchKernelGGL(exact_series_u8_seg_kernel, g3, blk, 0, s, reinterpret_cast<const uint8_t *>(data), ld,
-                               nchan, n, shifts, out, t_begin, t_len);
-            return launch_check("exact_series_u8_seg_kernel");
+    return with_dtype<uint8_t, float, double>("exact_series", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const T *x = reinterpret_cast<const T *>(data);
+        if constexpr (std::is_same_v<T, uint8_t>) {
+            if ((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (ld & 3) == 0) {
+                // integer channel segments, float64 atomics (exact: integer sums < 2^53)
+                PU_TRY_HIP(hipMemsetAsync(out, 0, (size_t)rows * (size_t)t_len * sizeof(double), s));
+                const dim3 g3(grid.x, grid.y, (unsigned)((nchan + kSegChans - 1) / kSegChans));
+                return launch("exact_series_u8_seg_kernel", exact_series_u8_seg_kernel, g3, blk, 0, s, x, ld, nchan, n,
+                              shifts, out, t_begin, t_len);
+            }
         }
-        hipLaunchKernelGGL(exact_series_kernel<uint8_t>, grid, blk, 0, s, reinterpret_cast<const uint8_t *>(data), ld,
-                           nchan, n, shifts, out, t_begin, t_len);
-        break;
-    case PU_F32:
-        hipLaunchKernelGGL(exact_series_kernel<float>, grid, blk, 0, s, reinterpret_cast<const float *>(data), ld,
-                           nchan, n, shifts, out, t_begin, t_len);
-        break;
-    case PU_F64:
-        hipLaunchKernelGGL(exact_series_kernel<double>, grid, blk, 0, s, reinterpret_cast<const double *>(data), ld,
-                           nchan, n, shifts, out, t_begin, t_len);
-        break;
-    default: set_error("exact_series: dtype %d", dtype); return PU_EUNSUPPORTED;
-    }
-    return launch_check("exact_series_kernel");
+        return launch("exact_series_kernel", exact_series_kernel<T>, grid, blk, 0, s, x, ld, nchan, n, shifts, out,
+                      t_begin, t_len);
+    });
 }
 
 int nan_rule(int64_t ndm, double *max_out, double *std_out, double *snr_out, int32_t *win_out, hipStream_t s)
 {
-    hipLaunchKernelGGL(nan_rule_kernel, dim3((unsigned)((ndm + 255) / 256)), dim3(256), 0, s, ndm, max_out, std_out,
-                       snr_out, win_out);
-    return launch_check("nan_rule_kernel");
+    return launch("nan_rule_kernel", nan_rule_kernel, dim3((unsigned)((ndm + 255) / 256)), dim3(256), 0, s, ndm, max_out,
+                  std_out, snr_out, win_out);
 }
 
 }  // namespace pu
@@ -686,13 +656,10 @@ int pu_series_stats(const double *series, int64_t rows, int64_t n, int64_t ld, c
     PU_REQUIRE(series && max_out && std_out && snr_out && rebin_out, "pu_series_stats: NULL pointer");
     PU_REQUIRE(rows > 0 && n > 0 && ld >= n, "pu_series_stats: bad shape");
     PU_REQUIRE(rows < (int64_t(1) << 31) && n < (int64_t(1) << 40), "pu_series_stats: too large");
-    PU_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
-               "pu_series_stats: workspace NULL or not 256-byte aligned");
-    // rows per batch: as many as the workspace holds
+    // rows per batch: as many as the workspace holds, one at the least
     int64_t per = rows;
     while (per > 1 && stats_bytes(per, n) > workspace_bytes) per = (per + 1) / 2;
-    PU_REQUIRE(stats_bytes(per, n) <= workspace_bytes, "pu_series_stats: workspace holds no row (%zu bytes)",
-               workspace_bytes);
+    if (int rc = pu::check_workspace("pu_series_stats", workspace, workspace_bytes, stats_bytes(per, n), 256)) return rc;
     hipStream_t s = pu::as_stream(stream);
     for (int64_t r0 = 0; r0 < rows; r0 += per) {
         const int64_t m = std::min(per, rows - r0);
@@ -721,15 +688,12 @@ int pu_series_events(const double *series, int64_t rows, int64_t n, int64_t ld, 
     PU_REQUIRE(rows < (int64_t(1) << 31) && n < (int64_t(1) << 40), "pu_series_events: too large");
     PU_REQUIRE(cap >= 0 && (events || cap == 0), "pu_series_events: cap < 0, or events NULL with cap > 0");
     PU_REQUIRE(std::isfinite(threshold) && threshold > 0.0, "pu_series_events: threshold must be finite and > 0");
-    PU_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
-               "pu_series_events: workspace NULL or not 256-byte aligned");
-    // rows per batch: as many as the workspace holds (and a launch's grid.y)
+    // rows per batch: as many as the workspace holds (and a launch's grid.y), one at the least
     int64_t per = std::min<int64_t>(rows, 32768);
     while (per > 1 && events_bytes(per, n) > workspace_bytes) per = (per + 1) / 2;
-    PU_REQUIRE(events_bytes(per, n) <= workspace_bytes, "pu_series_events: workspace holds no row (%zu bytes)",
-               workspace_bytes);
+    if (int rc = pu::check_workspace("pu_series_events", workspace, workspace_bytes, events_bytes(per, n), 256)) return rc;
     hipStream_t s = pu::as_stream(stream);
-    int64_t *total = carve(workspace, per, n, true).total;  // device: events delivered so far
+    int64_t *total = carve(pu::Carver(workspace), per, n, true).total;  // device: events delivered so far
     int rc = pu::hip_check(hipMemsetAsync(total, 0, sizeof(int64_t), s), "hipMemsetAsync(event total)");
     for (int64_t r0 = 0; r0 < rows && !rc; r0 += per) {
         const int64_t m = std::min(per, rows - r0);

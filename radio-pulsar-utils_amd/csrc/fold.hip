@@ -371,15 +371,6 @@ int fold_tile(int64_t pitch, size_t acc_bytes, bool full, size_t *lds)
     return 0;
 }
 
-template <typename Kern>
-int fold_ensure_lds(Kern kern, size_t bytes)
-{
-    if (bytes <= FOLD_LDS_SMALL) return PU_OK;
-    return pu::hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
-                         "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-}
-
 // ------------------------------------------------------------------ H-test
 
 constexpr int HT_MAX_N = 8192;
@@ -482,7 +473,21 @@ __global__ void __launch_bounds__(256) htest_final_kernel(const double *__restri
     if (tid == 0) h[row] = best, mo[row] = bestm;
 }
 
-size_t htest_table_bytes(int64_t n) { return ((size_t)n * sizeof(double2) + 255) & ~(size_t)255; }
+// pu_h_test's workspace: the table of n (cos, sin) pairs, then rows x nmax harmonic powers
+struct HtestWs {
+    double2 *tab;
+    double *pw;
+    size_t bytes;
+};
+
+HtestWs htest_carve(pu::Carver c, int64_t rows, int64_t n, int64_t nmax)
+{
+    HtestWs w;
+    w.tab = c.take<double2>((size_t)n * sizeof(double2), 16);
+    w.pw = c.take<double>((size_t)rows * (size_t)nmax * sizeof(double));
+    w.bytes = c.used();
+    return w;
+}
 
 }  // namespace
 
@@ -500,81 +505,75 @@ int pu_fold(const void *x, int dtype, int64_t nchan, int64_t n, int64_t ld, int6
             double dphase, int64_t nbin, double *sums, int64_t ld_sums, int64_t *counts, void *workspace,
             size_t workspace_bytes, void *stream)
 {
-    if (dtype != PU_U8 && dtype != PU_F32 && dtype != PU_F64) {
-        pu::set_error("pu_fold: unsupported dtype %d", dtype);
-        return PU_EUNSUPPORTED;
-    }
-    PU_REQUIRE(nbin >= 1, "pu_fold: nbin %lld < 1", (long long)nbin);
-    PU_REQUIRE(n >= 0 && nchan >= 0, "pu_fold: negative size (nchan %lld, n %lld)", (long long)nchan, (long long)n);
-    PU_REQUIRE(ld >= n && ld_sums >= nbin,
-               "pu_fold: leading dimension too small (ld %lld < n %lld or ld_sums %lld < nbin %lld)", (long long)ld,
-               (long long)n, (long long)ld_sums, (long long)nbin);
-    PU_REQUIRE(std::isfinite(phase0) && std::isfinite(dphase), "pu_fold: phase0 and dphase must be finite");
-    PU_REQUIRE(first_sample <= INT64_MAX - n, "pu_fold: first_sample + n overflows");
-    {
-        const double lim = 4503599627370496.0;  // 2^52: beyond it a phase has no fraction
-        const double pa = phase0 + (double)first_sample * dphase;
-        const double pb = phase0 + (double)(first_sample + (n > 0 ? n - 1 : 0)) * dphase;
-        PU_REQUIRE(std::fabs(pa) < lim && std::fabs(pb) < lim,
-                   "pu_fold: the phase reaches 2^52 in this chunk (%g .. %g): no fraction left to bin", pa, pb);
-    }
-    if (nbin > FOLD_MAX_NBIN) {
-        pu::set_error("pu_fold: nbin %lld above %d (the bins of a channel tile are LDS accumulators)", (long long)nbin,
-                      FOLD_MAX_NBIN);
-        return PU_EUNSUPPORTED;
-    }
-    if (n == 0 || nchan == 0) return PU_OK;
-    PU_REQUIRE(x && sums && counts, "pu_fold: null pointer");
-    const size_t need = pu_fold_workspace_bytes(nchan, n, nbin);
-    PU_REQUIRE(need != SIZE_MAX, "pu_fold: the partials of %lld x %lld x %lld overflow", (long long)nchan,
-               (long long)n, (long long)nbin);
-    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "pu_fold: workspace of %zu bytes (8-byte aligned) needed, got %zu", need, workspace_bytes);
-    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % pu::elem_size(dtype) == 0,
-               "pu_fold: x is not aligned to its element type");
-    size_t lds = 0;
-    const int tc = dtype == PU_U8 ? fold_tile(fold_pad((int)nbin), 4, false, &lds) : fold_tile(nbin, 8, true, &lds);
-    PU_REQUIRE(tc > 0, "pu_fold: nbin %lld does not fit the LDS", (long long)nbin);
-    const int64_t nseg = (n + FOLD_SEG - 1) / FOLD_SEG, nct = (nchan + tc - 1) / tc;
-    PU_REQUIRE(nseg <= INT32_MAX / nct && nchan <= INT32_MAX / nbin,
-               "pu_fold: %lld segments x %lld channel tiles exceed the grid limit", (long long)nseg, (long long)nct);
-    hipStream_t s = pu::as_stream(stream);
-    const dim3 grid((unsigned)(nseg * nct)), block(256);
-    const unsigned cgrid = (unsigned)((nchan * nbin + 255) / 256);
-    if (dtype == PU_U8) {
-        const uint8_t *p = static_cast<const uint8_t *>(x);
-        uint32_t *part = static_cast<uint32_t *>(workspace);
-        const bool vec = (reinterpret_cast<uintptr_t>(x) | static_cast<uintptr_t>(ld)) % 16 == 0;
-        if (vec) {
-            if (int rc = fold_ensure_lds(fold_u8_kernel<true>, lds)) return rc;
-            hipLaunchKernelGGL(fold_u8_kernel<true>, grid, block, lds, s, p, nchan, n, ld, first_sample, phase0, dphase, nbin, tc, nct, part);
-        } else {
-            if (int rc = fold_ensure_lds(fold_u8_kernel<false>, lds)) return rc;
-            hipLaunchKernelGGL(fold_u8_kernel<false>, grid, block, lds, s, p, nchan, n, ld, first_sample, phase0, dphase, nbin, tc, nct, part);
+    return pu::with_dtype<uint8_t, float, double>("pu_fold", dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        constexpr bool u8 = std::is_same_v<T, uint8_t>;
+        PU_REQUIRE(nbin >= 1, "pu_fold: nbin %lld < 1", (long long)nbin);
+        PU_REQUIRE(n >= 0 && nchan >= 0, "pu_fold: negative size (nchan %lld, n %lld)", (long long)nchan, (long long)n);
+        PU_REQUIRE(ld >= n && ld_sums >= nbin,
+                   "pu_fold: leading dimension too small (ld %lld < n %lld or ld_sums %lld < nbin %lld)", (long long)ld,
+                   (long long)n, (long long)ld_sums, (long long)nbin);
+        PU_REQUIRE(std::isfinite(phase0) && std::isfinite(dphase), "pu_fold: phase0 and dphase must be finite");
+        PU_REQUIRE(first_sample <= INT64_MAX - n, "pu_fold: first_sample + n overflows");
+        {
+            const double lim = 4503599627370496.0;  // 2^52: beyond it a phase has no fraction
+            const double pa = phase0 + (double)first_sample * dphase;
+            const double pb = phase0 + (double)(first_sample + (n > 0 ? n - 1 : 0)) * dphase;
+            PU_REQUIRE(std::fabs(pa) < lim && std::fabs(pb) < lim,
+                       "pu_fold: the phase reaches 2^52 in this chunk (%g .. %g): no fraction left to bin", pa, pb);
         }
-        if (int rc = pu::launch_check("fold_u8_kernel")) return rc;
-        hipLaunchKernelGGL(fold_combine_kernel<uint32_t>, dim3(cgrid), block, 0, s, part, nseg, nchan, nbin, sums, ld_sums);
-    } else {
-        double *part = static_cast<double *>(workspace);
-        if (dtype == PU_F32) {
-            if (int rc = fold_ensure_lds(fold_float_kernel<float>, lds)) return rc;
-            hipLaunchKernelGGL(fold_float_kernel<float>, grid, block, lds, s, static_cast<const float *>(x), nchan, n, ld, first_sample, phase0, dphase, nbin, tc, nct, part);
-        } else {
-            if (int rc = fold_ensure_lds(fold_float_kernel<double>, lds)) return rc;
-            hipLaunchKernelGGL(fold_float_kernel<double>, grid, block, lds, s, static_cast<const double *>(x), nchan, n, ld, first_sample, phase0, dphase, nbin, tc, nct, part);
+        if (nbin > FOLD_MAX_NBIN) {
+            pu::set_error("pu_fold: nbin %lld above %d (the bins of a channel tile are LDS accumulators)", (long long)nbin,
+                          FOLD_MAX_NBIN);
+            return PU_EUNSUPPORTED;
         }
-        if (int rc = pu::launch_check("fold_float_kernel")) return rc;
-        hipLaunchKernelGGL(fold_combine_kernel<double>, dim3(cgrid), block, 0, s, part, nseg, nchan, nbin, sums, ld_sums);
-    }
-    if (int rc = pu::launch_check("fold_combine_kernel")) return rc;
-    hipLaunchKernelGGL(fold_counts_kernel, dim3((unsigned)nseg), block, (size_t)nbin * 4, s, n, first_sample, phase0, dphase, nbin, counts);
-    return pu::launch_check("fold_counts_kernel");
+        if (n == 0 || nchan == 0) return PU_OK;
+        PU_REQUIRE(x && sums && counts, "pu_fold: null pointer");
+        const size_t need = pu_fold_workspace_bytes(nchan, n, nbin);
+        PU_REQUIRE(need != SIZE_MAX, "pu_fold: the partials of %lld x %lld x %lld overflow", (long long)nchan,
+                   (long long)n, (long long)nbin);
+        if (int rc = pu::check_workspace("pu_fold", workspace, workspace_bytes, need, 8)) return rc;
+        PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % sizeof(T) == 0, "pu_fold: x is not aligned to its element type");
+        size_t lds = 0;
+        const int tc = u8 ? fold_tile(fold_pad((int)nbin), 4, false, &lds) : fold_tile(nbin, 8, true, &lds);
+        PU_REQUIRE(tc > 0, "pu_fold: nbin %lld does not fit the LDS", (long long)nbin);
+        const int64_t nseg = (n + FOLD_SEG - 1) / FOLD_SEG, nct = (nchan + tc - 1) / tc;
+        PU_REQUIRE(nseg <= INT32_MAX / nct && nchan <= INT32_MAX / nbin,
+                   "pu_fold: %lld segments x %lld channel tiles exceed the grid limit", (long long)nseg, (long long)nct);
+        hipStream_t s = pu::as_stream(stream);
+        const dim3 grid((unsigned)(nseg * nct)), block(256);
+        const T *p = static_cast<const T *>(x);
+        // the partial sums: exact integers for 8-bit input, float64 otherwise
+        using P = std::conditional_t<u8, uint32_t, double>;
+        P *part = static_cast<P *>(workspace);
+        if constexpr (u8) {
+            // (either instance, then one check)
+            const bool vec = (reinterpret_cast<uintptr_t>(x) | static_cast<uintptr_t>(ld)) % 16 == 0;
+            if (vec) {
+                if (int rc = pu::ensure_lds(fold_u8_kernel<true>, lds)) return rc;
+                hipLaunchKernelGGL(fold_u8_kernel<true>, grid, block, lds, s, p, nchan, n, ld, first_sample, phase0, dphase, nbin, tc, nct, part);
+            } else {
+                if (int rc = pu::ensure_lds(fold_u8_kernel<false>, lds)) return rc;
+                hipLaunchKernelGGL(fold_u8_kernel<false>, grid, block, lds, s, p, nchan, n, ld, first_sample, phase0, dphase, nbin, tc, nct, part);
+            }
+            if (int rc = pu::launch_check("fold_u8_kernel")) return rc;
+        } else {
+            if (int rc = pu::launch("fold_float_kernel", fold_float_kernel<T>, grid, block, lds, s, p, nchan, n, ld, first_sample,
+                                    phase0, dphase, nbin, tc, nct, part))
+                return rc;
+        }
+        if (int rc = pu::launch("fold_combine_kernel", fold_combine_kernel<P>, dim3((unsigned)((nchan * nbin + 255) / 256)), block,
+                                0, s, part, nseg, nchan, nbin, sums, ld_sums))
+            return rc;
+        return pu::launch("fold_counts_kernel", fold_counts_kernel, dim3((unsigned)nseg), block, (size_t)nbin * 4, s, n,
+                          first_sample, phase0, dphase, nbin, counts);
+    });
 }
 
 size_t pu_h_test_workspace_bytes(int64_t rows, int64_t n, int64_t nmax)
 {
     if (rows <= 0 || n <= 0 || nmax <= 0 || n > HT_MAX_N || nmax > n) return 0;
-    return htest_table_bytes(n) + (size_t)rows * (size_t)nmax * sizeof(double);
+    return htest_carve(pu::Carver(), rows, n, nmax).bytes;
 }
 
 int pu_h_test(const double *profiles, int64_t rows, int64_t n, int64_t ld, int64_t nmax, double *h, int32_t *m,
@@ -597,18 +596,17 @@ int pu_h_test(const double *profiles, int64_t rows, int64_t n, int64_t ld, int64
     const int64_t kblocks = (nmax + 3) / 4;
     PU_REQUIRE(rows <= INT32_MAX / kblocks, "pu_h_test: %lld rows x %lld harmonics exceed the grid limit",
                (long long)rows, (long long)nmax);
-    const size_t need = pu_h_test_workspace_bytes(rows, n, nmax);
-    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
-               "pu_h_test: workspace of %zu bytes (16-byte aligned) needed, got %zu", need, workspace_bytes);
+    const HtestWs w = htest_carve(pu::Carver(workspace), rows, n, nmax);
+    if (int rc = pu::check_workspace("pu_h_test", workspace, workspace_bytes, w.bytes, 16)) return rc;
     hipStream_t s = pu::as_stream(stream);
-    double2 *tab = static_cast<double2 *>(workspace);
-    double *pw = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + htest_table_bytes(n));
-    hipLaunchKernelGGL(htest_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, tab);
-    if (int rc = pu::launch_check("htest_table_kernel")) return rc;
-    hipLaunchKernelGGL(htest_power_kernel, dim3((unsigned)(rows * kblocks)), dim3(256), 0, s, profiles, n, ld, nmax, kblocks, tab, pw);
-    if (int rc = pu::launch_check("htest_power_kernel")) return rc;
-    hipLaunchKernelGGL(htest_final_kernel, dim3((unsigned)rows), dim3(256), 0, s, profiles, n, ld, nmax, pw, h, m, zs, ld_zs);
-    return pu::launch_check("htest_final_kernel");
+    if (int rc = pu::launch("htest_table_kernel", htest_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n,
+                            w.tab))
+        return rc;
+    if (int rc = pu::launch("htest_power_kernel", htest_power_kernel, dim3((unsigned)(rows * kblocks)), dim3(256), 0, s,
+                            profiles, n, ld, nmax, kblocks, w.tab, w.pw))
+        return rc;
+    return pu::launch("htest_final_kernel", htest_final_kernel, dim3((unsigned)rows), dim3(256), 0, s, profiles, n, ld, nmax,
+                      w.pw, h, m, zs, ld_zs);
 }
 
 }  // extern "C"

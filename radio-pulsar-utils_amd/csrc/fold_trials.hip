@@ -273,78 +273,67 @@ int pu_fold_trials(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld
                    int64_t ld_trial, int64_t ld_row, int64_t *counts, void *workspace, size_t workspace_bytes,
                    void *stream)
 {
-    if (dtype != PU_F32 && dtype != PU_F64) {
-        pu::set_error("pu_fold_trials: unsupported dtype %d (a dedispersed series is float32 or float64)", dtype);
-        return PU_EUNSUPPORTED;
-    }
-    PU_REQUIRE(nbin >= 2, "pu_fold_trials: nbin %lld < 2", (long long)nbin);
-    PU_REQUIRE(n >= 0 && rows >= 0 && ntrials >= 0, "pu_fold_trials: negative size (rows %lld, n %lld, ntrials %lld)",
-               (long long)rows, (long long)n, (long long)ntrials);
-    PU_REQUIRE(ld >= n && ld_trial >= nbin && ntrials <= INT64_MAX / ld_trial && ld_row >= ntrials * ld_trial,
-               "pu_fold_trials: leading dimension too small (ld %lld < n %lld, ld_trial %lld < nbin %lld or ld_row %lld "
-               "< ntrials x ld_trial)", (long long)ld, (long long)n, (long long)ld_trial, (long long)nbin,
-               (long long)ld_row);
-    PU_REQUIRE(first_sample <= INT64_MAX - n, "pu_fold_trials: first_sample + n overflows");
-    if (nbin > FT_MAX_NBIN) {
-        pu::set_error("pu_fold_trials: nbin %lld above %d (a lane's bins are LDS accumulators: 64 x nbin x 8 bytes per "
-                      "wave within 144 KiB)", (long long)nbin, FT_MAX_NBIN);
-        return PU_EUNSUPPORTED;
-    }
-    if (n == 0 || rows == 0 || ntrials == 0) return PU_OK;
-    const int64_t el = ft_partials(rows, n, ntrials, nbin);
-    PU_REQUIRE(el >= 0, "pu_fold_trials: the partials of %lld x %lld x %lld x %lld overflow", (long long)rows,
-               (long long)n, (long long)ntrials, (long long)nbin);
-    const size_t need = (size_t)el * 8;
-    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "pu_fold_trials: workspace of %zu bytes (8-byte aligned) needed, got %zu", need, workspace_bytes);
-    PU_REQUIRE(x && dphase && sums && counts, "pu_fold_trials: null pointer");
-    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % pu::elem_size(dtype) == 0,
-               "pu_fold_trials: x is not aligned to its element type");
-    const int w = ft_waves(nbin), tl = 64 * w;
-    const int64_t nseg = (n + FT_SEG - 1) / FT_SEG, nkt = (ntrials + tl - 1) / tl;
-    PU_REQUIRE(nseg <= INT32_MAX / nkt && nseg * nkt <= INT32_MAX / rows && el / nseg <= INT32_MAX * (int64_t)128,
-               "pu_fold_trials: %lld rows x %lld segments x %lld trial tiles exceed the grid limit", (long long)rows,
-               (long long)nseg, (long long)nkt);
-    // float64 sample indices by adding 1.0 while every index of the chunk is below 2^53
-    const int64_t big = (int64_t)1 << 53;
-    const bool inc = first_sample > -big && first_sample + n < big;
-    const size_t lds = (size_t)FT_SUB * 8 + (size_t)tl * nbin * 8, clds = (size_t)tl * nbin * 4;
-    hipStream_t s = pu::as_stream(stream);
-    const dim3 grid((unsigned)(rows * nseg * nkt)), block(tl);
-    double *part = static_cast<double *>(workspace);
-    const int nb = (int)nbin;
-#define FT_LAUNCH(T, INC)                                                                                              \
-    do {                                                                                                               \
-        if (lds > 64 * 1024)                                                                                           \
-            PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ft_fold_kernel<T, INC>),                     \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
-        hipLaunchKernelGGL((ft_fold_kernel<T, INC>), grid, block, lds, s, static_cast<const T *>(x), n, ld,            \
-                           first_sample, phase0, dphase, ntrials, nb, nkt, nseg, part);                                \
-    } while (0)
-    if (dtype == PU_F32) {
-        if (inc) FT_LAUNCH(float, true); else FT_LAUNCH(float, false);
-    } else {
-        if (inc) FT_LAUNCH(double, true); else FT_LAUNCH(double, false);
-    }
-#undef FT_LAUNCH
-    if (int rc = pu::launch_check("ft_fold_kernel")) return rc;
-    const unsigned cgrid = (unsigned)((rows * ntrials * nbin + 255) / 256);
-    hipLaunchKernelGGL(ft_combine_kernel, dim3(cgrid), dim3(256), 0, s, part, nseg, rows, ntrials, nb, n, first_sample,
-                       phase0, dphase, sums, ld_trial, ld_row);
-    if (int rc = pu::launch_check("ft_combine_kernel")) return rc;
-    const dim3 hgrid((unsigned)(nseg * nkt));
-    if (inc) {
-        if (clds > 64 * 1024)
-            PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ft_counts_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));
-        hipLaunchKernelGGL(ft_counts_kernel<true>, hgrid, block, clds, s, n, first_sample, phase0, dphase, ntrials, nb, nkt, counts);
-    } else {
-        if (clds > 64 * 1024)
-            PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ft_counts_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));
-        hipLaunchKernelGGL(ft_counts_kernel<false>, hgrid, block, clds, s, n, first_sample, phase0, dphase, ntrials, nb, nkt, counts);
-    }
-    return pu::launch_check("ft_counts_kernel");
+    // (a dedispersed series is float32 or float64)
+    return pu::with_dtype<float, double>("pu_fold_trials", dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        PU_REQUIRE(nbin >= 2, "pu_fold_trials: nbin %lld < 2", (long long)nbin);
+        PU_REQUIRE(n >= 0 && rows >= 0 && ntrials >= 0, "pu_fold_trials: negative size (rows %lld, n %lld, ntrials %lld)",
+                   (long long)rows, (long long)n, (long long)ntrials);
+        PU_REQUIRE(ld >= n && ld_trial >= nbin && ntrials <= INT64_MAX / ld_trial && ld_row >= ntrials * ld_trial,
+                   "pu_fold_trials: leading dimension too small (ld %lld < n %lld, ld_trial %lld < nbin %lld or ld_row %lld "
+                   "< ntrials x ld_trial)", (long long)ld, (long long)n, (long long)ld_trial, (long long)nbin,
+                   (long long)ld_row);
+        PU_REQUIRE(first_sample <= INT64_MAX - n, "pu_fold_trials: first_sample + n overflows");
+        if (nbin > FT_MAX_NBIN) {
+            pu::set_error("pu_fold_trials: nbin %lld above %d (a lane's bins are LDS accumulators: 64 x nbin x 8 bytes per "
+                          "wave within 144 KiB)", (long long)nbin, FT_MAX_NBIN);
+            return PU_EUNSUPPORTED;
+        }
+        if (n == 0 || rows == 0 || ntrials == 0) return PU_OK;
+        const int64_t el = ft_partials(rows, n, ntrials, nbin);
+        PU_REQUIRE(el >= 0, "pu_fold_trials: the partials of %lld x %lld x %lld x %lld overflow", (long long)rows,
+                   (long long)n, (long long)ntrials, (long long)nbin);
+        const size_t need = (size_t)el * 8;
+        if (int rc = pu::check_workspace("pu_fold_trials", workspace, workspace_bytes, need, 8)) return rc;
+        PU_REQUIRE(x && dphase && sums && counts, "pu_fold_trials: null pointer");
+        PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % sizeof(T) == 0, "pu_fold_trials: x is not aligned to its element type");
+        const int w = ft_waves(nbin), tl = 64 * w;
+        const int64_t nseg = (n + FT_SEG - 1) / FT_SEG, nkt = (ntrials + tl - 1) / tl;
+        PU_REQUIRE(nseg <= INT32_MAX / nkt && nseg * nkt <= INT32_MAX / rows && el / nseg <= INT32_MAX * (int64_t)128,
+                   "pu_fold_trials: %lld rows x %lld segments x %lld trial tiles exceed the grid limit", (long long)rows,
+                   (long long)nseg, (long long)nkt);
+        // float64 sample indices by adding 1.0 while every index of the chunk is below 2^53
+        const int64_t big = (int64_t)1 << 53;
+        const bool inc = first_sample > -big && first_sample + n < big;
+        const size_t lds = (size_t)FT_SUB * 8 + (size_t)tl * nbin * 8, clds = (size_t)tl * nbin * 4;
+        hipStream_t s = pu::as_stream(stream);
+        const dim3 grid((unsigned)(rows * nseg * nkt)), block(tl);
+        double *part = static_cast<double *>(workspace);
+        const int nb = (int)nbin;
+        const T *xs = static_cast<const T *>(x);
+        // (either instance, then one check)
+        if (inc) {
+            if (int rc = pu::ensure_lds(ft_fold_kernel<T, true>, lds)) return rc;
+            hipLaunchKernelGGL((ft_fold_kernel<T, true>), grid, block, lds, s, xs, n, ld, first_sample, phase0, dphase, ntrials, nb, nkt, nseg, part);
+        } else {
+            if (int rc = pu::ensure_lds(ft_fold_kernel<T, false>, lds)) return rc;
+            hipLaunchKernelGGL((ft_fold_kernel<T, false>), grid, block, lds, s, xs, n, ld, first_sample, phase0, dphase, ntrials, nb, nkt, nseg, part);
+        }
+        if (int rc = pu::launch_check("ft_fold_kernel")) return rc;
+        const unsigned cgrid = (unsigned)((rows * ntrials * nbin + 255) / 256);
+        if (int rc = pu::launch("ft_combine_kernel", ft_combine_kernel, dim3(cgrid), dim3(256), 0, s, part, nseg, rows, ntrials, nb,
+                                n, first_sample, phase0, dphase, sums, ld_trial, ld_row))
+            return rc;
+        const dim3 hgrid((unsigned)(nseg * nkt));
+        if (inc) {
+            if (int rc = pu::ensure_lds(ft_counts_kernel<true>, clds)) return rc;
+            hipLaunchKernelGGL(ft_counts_kernel<true>, hgrid, block, clds, s, n, first_sample, phase0, dphase, ntrials, nb, nkt, counts);
+        } else {
+            if (int rc = pu::ensure_lds(ft_counts_kernel<false>, clds)) return rc;
+            hipLaunchKernelGGL(ft_counts_kernel<false>, hgrid, block, clds, s, n, first_sample, phase0, dphase, ntrials, nb, nkt, counts);
+        }
+        return pu::launch_check("ft_counts_kernel");
+    });
 }
 
 int pu_profile_chi2(const double *sums, int64_t ld_trial, int64_t ld_row, const int64_t *counts, int64_t rows,
@@ -362,9 +351,8 @@ int pu_profile_chi2(const double *sums, int64_t ld_trial, int64_t ld_row, const 
     PU_REQUIRE(sums && counts && mean && var && chi2 && dof, "pu_profile_chi2: null pointer");
     PU_REQUIRE(rows <= INT32_MAX * (int64_t)256 / ntrials, "pu_profile_chi2: %lld rows x %lld trials exceed the grid limit",
                (long long)rows, (long long)ntrials);
-    hipLaunchKernelGGL(chi2_kernel, dim3((unsigned)((rows * ntrials + 255) / 256)), dim3(256), 0, pu::as_stream(stream),
-                       sums, ld_trial, ld_row, counts, rows, ntrials, (int)nbin, mean, var, chi2, dof);
-    return pu::launch_check("chi2_kernel");
+    return pu::launch("chi2_kernel", chi2_kernel, dim3((unsigned)((rows * ntrials + 255) / 256)), dim3(256), 0,
+                      pu::as_stream(stream), sums, ld_trial, ld_row, counts, rows, ntrials, (int)nbin, mean, var, chi2, dof);
 }
 
 }  // extern "C"

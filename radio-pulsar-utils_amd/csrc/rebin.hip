@@ -365,15 +365,6 @@ __global__ void __launch_bounds__(256) scale_transpose_f32_kernel(const T *__res
     }
 }
 
-template <typename T, int E>
-void launch_quantize_pack(unsigned grid, hipStream_t s, const void *src, int64_t nchans, int64_t nsamps, int64_t ld_src,
-                          const double *scale, const double *offset, int nbits, uint8_t *dst, int64_t ld_dst,
-                          int64_t row_bytes, int64_t nct, int dalign)
-{
-    hipLaunchKernelGGL((quantize_pack_kernel<T, E>), dim3(grid), dim3(256), 0, s, static_cast<const T *>(src), nchans,
-                       nsamps, ld_src, scale, offset, nbits, dst, ld_dst, row_bytes, nct, dalign);
-}
-
 }  // namespace
 
 extern "C" {
@@ -386,66 +377,51 @@ int pu_quantize_pack_transpose(const void *src, int dtype, int64_t nchans, int64
         pu::set_error("pu_quantize_pack_transpose: nbits %d unsupported (1, 2, 4, 8, 32)", nbits);
         return PU_EUNSUPPORTED;
     }
-    if (dtype != PU_U8 && dtype != PU_F32 && dtype != PU_F64) {
-        pu::set_error("pu_quantize_pack_transpose: unsupported dtype %d", dtype);
-        return PU_EUNSUPPORTED;
-    }
-    PU_REQUIRE(src && dst && nsamps >= 0 && nchans >= 0 && nchans <= INT64_MAX / 32,
-               "pu_quantize_pack_transpose: bad arguments");
-    PU_REQUIRE((scale == nullptr) == (offset == nullptr),
-               "pu_quantize_pack_transpose: scale and offset go together (both, or both NULL for identity)");
-    PU_REQUIRE(nchans * nbits % 8 == 0,
-               "pu_quantize_pack_transpose: nchans %lld x nbits %d is not a whole number of bytes", (long long)nchans,
-               nbits);
-    const int64_t row_bytes = nchans * nbits / 8;
-    PU_REQUIRE(ld_src >= nsamps && ld_dst >= row_bytes,
-               "pu_quantize_pack_transpose: leading dimension too small (ld_src %lld < %lld samples or ld_dst %lld < "
-               "%lld row bytes)", (long long)ld_src, (long long)nsamps, (long long)ld_dst, (long long)row_bytes);
-    const uintptr_t esize = pu::elem_size(dtype);
-    const uintptr_t sa = reinterpret_cast<uintptr_t>(src), da = reinterpret_cast<uintptr_t>(dst);
-    PU_REQUIRE(sa % esize == 0, "pu_quantize_pack_transpose: src is not aligned to its element type");
-    PU_REQUIRE(nbits != 32 || ((da | static_cast<uintptr_t>(ld_dst)) % 4 == 0),
-               "pu_quantize_pack_transpose: float32 rows need dst and ld_dst in multiples of 4 bytes");
-    if (nsamps == 0 || nchans == 0) return PU_OK;
-    const int tc = nbits == 32 ? 64 : QP_TC, tt = nbits == 32 ? 64 : QP_TT;
-    const int64_t nct = (nchans + tc - 1) / tc, ntt = (nsamps + tt - 1) / tt;
-    PU_REQUIRE(ntt <= INT32_MAX / nct, "pu_quantize_pack_transpose: %lld x %lld tiles exceed the grid limit",
-               (long long)ntt, (long long)nct);
-    const unsigned grid = (unsigned)(nct * ntt);
-    hipStream_t s = pu::as_stream(stream);
-    uint8_t *d = static_cast<uint8_t *>(dst);
-    if (nbits == 32) {
-        const dim3 g(grid), b(256);
-        switch (dtype) {
-        case PU_U8: hipLaunchKernelGGL(scale_transpose_f32_kernel<uint8_t>, g, b, 0, s, (const uint8_t *)src, nchans, nsamps, ld_src, scale, offset, d, ld_dst, nct); break;
-        case PU_F32: hipLaunchKernelGGL(scale_transpose_f32_kernel<float>, g, b, 0, s, (const float *)src, nchans, nsamps, ld_src, scale, offset, d, ld_dst, nct); break;
-        default: hipLaunchKernelGGL(scale_transpose_f32_kernel<double>, g, b, 0, s, (const double *)src, nchans, nsamps, ld_src, scale, offset, d, ld_dst, nct); break;
-        }
-        return pu::launch_check("scale_transpose_f32_kernel");
-    }
-    // the widest piece that src and every row start are aligned to; the widest store dst allows
-    const uintptr_t a = sa | (static_cast<uintptr_t>(ld_src) * esize);
-    const int w = a % 16 == 0 ? 16 : a % 4 == 0 ? 4 : 1;
-    const uintptr_t ad = da | static_cast<uintptr_t>(ld_dst);
-    const int dalign = ad % 16 == 0 ? 16 : ad % 8 == 0 ? 8 : ad % 4 == 0 ? 4 : ad % 2 == 0 ? 2 : 1;
-#define PU_QP_ARGS grid, s, src, nchans, nsamps, ld_src, scale, offset, nbits, d, ld_dst, row_bytes, nct, dalign
-    switch (dtype) {
-    case PU_U8:
-        if (w == 16) launch_quantize_pack<uint8_t, 16>(PU_QP_ARGS);
-        else if (w == 4) launch_quantize_pack<uint8_t, 4>(PU_QP_ARGS);
-        else launch_quantize_pack<uint8_t, 1>(PU_QP_ARGS);
-        break;
-    case PU_F32:
-        if (w == 16) launch_quantize_pack<float, 4>(PU_QP_ARGS);
-        else launch_quantize_pack<float, 1>(PU_QP_ARGS);
-        break;
-    default:
-        if (w == 16) launch_quantize_pack<double, 2>(PU_QP_ARGS);
-        else launch_quantize_pack<double, 1>(PU_QP_ARGS);
-        break;
-    }
-#undef PU_QP_ARGS
-    return pu::launch_check("quantize_pack_kernel");
+    return pu::with_dtype<uint8_t, float, double>("pu_quantize_pack_transpose", dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        PU_REQUIRE(src && dst && nsamps >= 0 && nchans >= 0 && nchans <= INT64_MAX / 32,
+                   "pu_quantize_pack_transpose: bad arguments");
+        PU_REQUIRE((scale == nullptr) == (offset == nullptr),
+                   "pu_quantize_pack_transpose: scale and offset go together (both, or both NULL for identity)");
+        PU_REQUIRE(nchans * nbits % 8 == 0,
+                   "pu_quantize_pack_transpose: nchans %lld x nbits %d is not a whole number of bytes", (long long)nchans,
+                   nbits);
+        const int64_t row_bytes = nchans * nbits / 8;
+        PU_REQUIRE(ld_src >= nsamps && ld_dst >= row_bytes,
+                   "pu_quantize_pack_transpose: leading dimension too small (ld_src %lld < %lld samples or ld_dst %lld < "
+                   "%lld row bytes)", (long long)ld_src, (long long)nsamps, (long long)ld_dst, (long long)row_bytes);
+        const uintptr_t esize = sizeof(T);
+        const uintptr_t sa = reinterpret_cast<uintptr_t>(src), da = reinterpret_cast<uintptr_t>(dst);
+        PU_REQUIRE(sa % esize == 0, "pu_quantize_pack_transpose: src is not aligned to its element type");
+        PU_REQUIRE(nbits != 32 || ((da | static_cast<uintptr_t>(ld_dst)) % 4 == 0),
+                   "pu_quantize_pack_transpose: float32 rows need dst and ld_dst in multiples of 4 bytes");
+        if (nsamps == 0 || nchans == 0) return PU_OK;
+        const int tc = nbits == 32 ? 64 : QP_TC, tt = nbits == 32 ? 64 : QP_TT;
+        const int64_t nct = (nchans + tc - 1) / tc, ntt = (nsamps + tt - 1) / tt;
+        PU_REQUIRE(ntt <= INT32_MAX / nct, "pu_quantize_pack_transpose: %lld x %lld tiles exceed the grid limit",
+                   (long long)ntt, (long long)nct);
+        const unsigned grid = (unsigned)(nct * ntt);
+        hipStream_t s = pu::as_stream(stream);
+        const T *p = static_cast<const T *>(src);
+        uint8_t *d = static_cast<uint8_t *>(dst);
+        if (nbits == 32)
+            return pu::launch("scale_transpose_f32_kernel", scale_transpose_f32_kernel<T>, dim3(grid), dim3(256), 0, s, p, nchans,
+                              nsamps, ld_src, scale, offset, d, ld_dst, nct);
+        // the widest piece that src and every row start are aligned to; the widest store dst allows
+        const uintptr_t a = sa | (static_cast<uintptr_t>(ld_src) * esize);
+        const int w = a % 16 == 0 ? 16 : a % 4 == 0 ? 4 : 1;
+        const uintptr_t ad = da | static_cast<uintptr_t>(ld_dst);
+        const int dalign = ad % 16 == 0 ? 16 : ad % 8 == 0 ? 8 : ad % 4 == 0 ? 4 : ad % 2 == 0 ? 2 : 1;
+        // E elements per piece: 16 bytes' worth, for 8-bit input 4 bytes' worth too, else 1
+        auto go = [&](auto e) {
+            return pu::launch("quantize_pack_kernel", quantize_pack_kernel<T, decltype(e)::value>, dim3(grid), dim3(256), 0, s, p,
+                              nchans, nsamps, ld_src, scale, offset, nbits, d, ld_dst, row_bytes, nct, dalign);
+        };
+        if (w == 16) return go(std::integral_constant<int, 16 / sizeof(T)>{});
+        if constexpr (sizeof(T) == 1)
+            if (w == 4) return go(std::integral_constant<int, 4>{});
+        return go(std::integral_constant<int, 1>{});
+    });
 }
 
 int pu_unpack_transpose(const void *src, int nbits, int64_t nsamps, int64_t nchans, int64_t ld_src, uint8_t *dst,
@@ -510,14 +486,10 @@ int pu_rebin_time(const void *x, int dtype, int64_t nrows, int64_t n, int64_t ld
     if (nout == 0) return PU_OK;
     const dim3 g(nblocks(nout, 256), (unsigned)nrows), b(256);
     hipStream_t s = pu::as_stream(stream);
-    switch (dtype) {
-    case PU_U8: hipLaunchKernelGGL(rebin_time_kernel<uint8_t>, g, b, 0, s, (const uint8_t *)x, nrows, nout, ld, w, out); break;
-    case PU_F32: hipLaunchKernelGGL(rebin_time_kernel<float>, g, b, 0, s, (const float *)x, nrows, nout, ld, w, out); break;
-    case PU_F64: hipLaunchKernelGGL(rebin_time_kernel<double>, g, b, 0, s, (const double *)x, nrows, nout, ld, w, out); break;
-    case PU_I64: hipLaunchKernelGGL(rebin_time_kernel<int64_t>, g, b, 0, s, (const int64_t *)x, nrows, nout, ld, w, out); break;
-    default: pu::set_error("pu_rebin_time: unsupported dtype %d", dtype); return PU_EUNSUPPORTED;
-    }
-    return pu::launch_check("rebin_time_kernel");
+    return pu::with_dtype<uint8_t, float, double, int64_t>("pu_rebin_time", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return pu::launch("rebin_time_kernel", rebin_time_kernel<T>, g, b, 0, s, (const T *)x, nrows, nout, ld, w, out);
+    });
 }
 
 int pu_rebin_chan(const void *x, int dtype, int64_t nrows, int64_t n, int64_t ld, int64_t rb, void *out, void *stream)
@@ -528,14 +500,12 @@ int pu_rebin_chan(const void *x, int dtype, int64_t nrows, int64_t n, int64_t ld
     PU_REQUIRE(ng < 65536, "pu_rebin_chan: at most 65535 output rows");
     const dim3 g(nblocks(n, 256), (unsigned)ng), b(256);
     hipStream_t s = pu::as_stream(stream);
-    switch (dtype) {
-    case PU_U8: hipLaunchKernelGGL((rebin_chan_kernel<uint8_t, uint64_t>), g, b, 0, s, (const uint8_t *)x, n, ld, rb, (uint64_t *)out); break;
-    case PU_F32: hipLaunchKernelGGL((rebin_chan_kernel<float, float>), g, b, 0, s, (const float *)x, n, ld, rb, (float *)out); break;
-    case PU_F64: hipLaunchKernelGGL((rebin_chan_kernel<double, double>), g, b, 0, s, (const double *)x, n, ld, rb, (double *)out); break;
-    case PU_I64: hipLaunchKernelGGL((rebin_chan_kernel<int64_t, int64_t>), g, b, 0, s, (const int64_t *)x, n, ld, rb, (int64_t *)out); break;
-    default: pu::set_error("pu_rebin_chan: unsupported dtype %d", dtype); return PU_EUNSUPPORTED;
-    }
-    return pu::launch_check("rebin_chan_kernel");
+    return pu::with_dtype<uint8_t, float, double, int64_t>("pu_rebin_chan", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        // 8-bit rows sum to uint64, every other type to itself
+        using To = std::conditional_t<std::is_same_v<T, uint8_t>, uint64_t, T>;
+        return pu::launch("rebin_chan_kernel", rebin_chan_kernel<T, To>, g, b, 0, s, (const T *)x, n, ld, rb, (To *)out);
+    });
 }
 
 int pu_roll_rows(const void *x, int dtype, int64_t nrows, int64_t n, int64_t ld, const int64_t *shifts, void *out,
@@ -560,14 +530,10 @@ int pu_roll_and_sum(const void *x, int dtype, int64_t n, int64_t roll, double *s
     PU_REQUIRE(roll >= 0 && roll < n, "pu_roll_and_sum: roll %lld outside [0, %lld)", (long long)roll, (long long)n);
     const dim3 g(nblocks(n, 256)), b(256);
     hipStream_t s = pu::as_stream(stream);
-    switch (dtype) {
-    case PU_U8: hipLaunchKernelGGL(roll_and_sum_kernel<uint8_t>, g, b, 0, s, (const uint8_t *)x, n, roll, sum); break;
-    case PU_F32: hipLaunchKernelGGL(roll_and_sum_kernel<float>, g, b, 0, s, (const float *)x, n, roll, sum); break;
-    case PU_F64: hipLaunchKernelGGL(roll_and_sum_kernel<double>, g, b, 0, s, (const double *)x, n, roll, sum); break;
-    case PU_I64: hipLaunchKernelGGL(roll_and_sum_kernel<int64_t>, g, b, 0, s, (const int64_t *)x, n, roll, sum); break;
-    default: pu::set_error("pu_roll_and_sum: unsupported dtype %d", dtype); return PU_EUNSUPPORTED;
-    }
-    return pu::launch_check("roll_and_sum_kernel");
+    return pu::with_dtype<uint8_t, float, double, int64_t>("pu_roll_and_sum", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return pu::launch("roll_and_sum_kernel", roll_and_sum_kernel<T>, g, b, 0, s, (const T *)x, n, roll, sum);
+    });
 }
 
 }  // extern "C"

@@ -269,7 +269,22 @@ resample_accel_kernel(const T *__restrict__ x, int64_t rows, int64_t n, int64_t 
 
 bool rf_valid_nfft(int64_t nfft) { return nfft >= 256 && nfft <= ((int64_t)1 << 24) && (nfft & (nfft - 1)) == 0; }
 
-size_t rf_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// The workspace: the twiddle table of nfft / 2 entries, then (four-step lengths only) the
+// first pass's columns, nfft / 2 per row.
+struct RfWs {
+    float2 *tbl, *tws;
+    size_t bytes;
+};
+
+RfWs rf_carve(pu::Carver c, int64_t rows, int64_t nfft)
+{
+    const size_t half = (size_t)(nfft / 2) * sizeof(float2);
+    RfWs w;
+    w.tbl = c.take<float2>(half);
+    w.tws = c.take<float2>(rf_shape(nfft).l1 ? (size_t)rows * half : 0);
+    w.bytes = c.used();
+    return w;
+}
 
 // pu_rfft (MAP = RfPlain) and pu_rfft_accel (RfAccel) over vrows output rows: every check, then
 // the launches.  ``who`` names the entry point in the messages.
@@ -277,75 +292,51 @@ template <typename MAP>
 int rf_transform(const char *who, const void *x, int dtype, int64_t vrows, int64_t n, int64_t ld, const double *mean,
                  int64_t nfft, void *spec, int64_t ld_spec, void *workspace, size_t workspace_bytes, void *stream, MAP map)
 {
-    if (dtype != PU_F32 && dtype != PU_F64) {
-        pu::set_error("%s: unsupported dtype %d (a dedispersed series is float32 or float64)", who, dtype);
-        return PU_EUNSUPPORTED;
-    }
-    PU_REQUIRE(rf_valid_nfft(nfft), "%s: nfft %lld is not a power of two in [2^8, 2^24]", who, (long long)nfft);
-    PU_REQUIRE(vrows >= 0 && n >= 0 && n <= nfft, "%s: bad size (rows %lld, n %lld, nfft %lld)", who, (long long)vrows,
-               (long long)n, (long long)nfft);
-    PU_REQUIRE(ld >= n && ld_spec >= nfft / 2 + 1, "%s: leading dimension too small (ld %lld < n %lld or ld_spec "
-               "%lld < nfft / 2 + 1)", who, (long long)ld, (long long)n, (long long)ld_spec);
-    if (vrows == 0) return PU_OK;
-    const RfShape sh = rf_shape(nfft);
-    const int64_t m = nfft / 2;
-    const int64_t groups = sh.l1 ? ((int64_t)1 << (sh.l1 - sh.lr)) : 1, cgroups = sh.l1 ? ((int64_t)1 << (sh.l2 - sh.lc)) : 1;
-    PU_REQUIRE(vrows <= 65535 && vrows <= INT32_MAX / groups && vrows <= INT32_MAX / cgroups,
-               "%s: %lld rows exceed the grid limit (65535 per call)", who, (long long)vrows);
-    const size_t need = pu_rfft_workspace_bytes(vrows, nfft);
-    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
-               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", who, need, workspace_bytes);
-    PU_REQUIRE(x && spec, "%s: null pointer", who);
-    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % pu::elem_size(dtype) == 0 && reinterpret_cast<uintptr_t>(spec) % 8 == 0,
-               "%s: x or spec is not aligned to its element type", who);
-    hipStream_t s = pu::as_stream(stream);
-    float2 *tbl = static_cast<float2 *>(workspace);
-    float2 *tws = reinterpret_cast<float2 *>(static_cast<unsigned char *>(workspace) + rf_up256((size_t)m * sizeof(float2)));
-    float2 *out = static_cast<float2 *>(spec);
-    hipLaunchKernelGGL(rfft_twiddle_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, tbl, nfft);
-    if (int rc = pu::launch_check("rfft_twiddle_kernel")) return rc;
-    const int n2 = 1 << sh.l2, nr = 1 << sh.lr;
-    const size_t lds_rows = ((size_t)nr * (n2 + 1) + n2 / 2) * sizeof(float2);
-#define RF_ATTR(K, BYTES)                                                                                              \
-    do {                                                                                                               \
-        if ((BYTES) > 64 * 1024)                                                                                       \
-            PU_TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                           (int)(BYTES)));                                                             \
-    } while (0)
-    if (sh.l1 == 0) {
-        if (dtype == PU_F32) {
-            RF_ATTR((rfft_rows_kernel<float, MAP, true>), lds_rows);
-            hipLaunchKernelGGL((rfft_rows_kernel<float, MAP, true>), dim3((unsigned)vrows), dim3(RF_THREADS), lds_rows, s,
-                               static_cast<const float *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec, map);
+    // (a dedispersed series is float32 or float64)
+    return pu::with_dtype<float, double>(who, dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        PU_REQUIRE(rf_valid_nfft(nfft), "%s: nfft %lld is not a power of two in [2^8, 2^24]", who, (long long)nfft);
+        PU_REQUIRE(vrows >= 0 && n >= 0 && n <= nfft, "%s: bad size (rows %lld, n %lld, nfft %lld)", who, (long long)vrows,
+                   (long long)n, (long long)nfft);
+        PU_REQUIRE(ld >= n && ld_spec >= nfft / 2 + 1, "%s: leading dimension too small (ld %lld < n %lld or ld_spec "
+                   "%lld < nfft / 2 + 1)", who, (long long)ld, (long long)n, (long long)ld_spec);
+        if (vrows == 0) return PU_OK;
+        const RfShape sh = rf_shape(nfft);
+        const int64_t m = nfft / 2;
+        const int64_t groups = sh.l1 ? ((int64_t)1 << (sh.l1 - sh.lr)) : 1, cgroups = sh.l1 ? ((int64_t)1 << (sh.l2 - sh.lc)) : 1;
+        PU_REQUIRE(vrows <= 65535 && vrows <= INT32_MAX / groups && vrows <= INT32_MAX / cgroups,
+                   "%s: %lld rows exceed the grid limit (65535 per call)", who, (long long)vrows);
+        if (int rc = pu::check_workspace(who, workspace, workspace_bytes, pu_rfft_workspace_bytes(vrows, nfft), 256)) return rc;
+        PU_REQUIRE(x && spec, "%s: null pointer", who);
+        PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(spec) % 8 == 0,
+                   "%s: x or spec is not aligned to its element type", who);
+        hipStream_t s = pu::as_stream(stream);
+        const RfWs w = rf_carve(pu::Carver(workspace), vrows, nfft);
+        const T *xs = static_cast<const T *>(x);
+        float2 *out = static_cast<float2 *>(spec);
+        if (int rc = pu::launch("rfft_twiddle_kernel", rfft_twiddle_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s,
+                                w.tbl, nfft))
+            return rc;
+        const int n2 = 1 << sh.l2, nr = 1 << sh.lr;
+        const size_t lds_rows = ((size_t)nr * (n2 + 1) + n2 / 2) * sizeof(float2);
+        if (sh.l1 == 0) {
+            if (int rc = pu::launch("rfft_rows_kernel", rfft_rows_kernel<T, MAP, true>, dim3((unsigned)vrows), dim3(RF_THREADS),
+                                    lds_rows, s, xs, n, ld, mean, sh, w.tbl, nullptr, out, ld_spec, map))
+                return rc;
         } else {
-            RF_ATTR((rfft_rows_kernel<double, MAP, true>), lds_rows);
-            hipLaunchKernelGGL((rfft_rows_kernel<double, MAP, true>), dim3((unsigned)vrows), dim3(RF_THREADS), lds_rows, s,
-                               static_cast<const double *>(x), n, ld, mean, sh, tbl, nullptr, out, ld_spec, map);
+            const size_t lds_cols = ((size_t)RF_TILE + ((size_t)1 << sh.l1) / 2) * sizeof(float2);
+            const dim3 cgrid((unsigned)(vrows * cgroups)), rgrid((unsigned)(vrows * groups));
+            if (int rc = pu::launch("rfft_cols_kernel", rfft_cols_kernel<T, MAP>, cgrid, dim3(RF_THREADS), lds_cols, s, xs, n, ld,
+                                    mean, sh, w.tbl, w.tws, map))
+                return rc;
+            // the second pass reads the workspace, never x: one instance serves both entry points
+            if (int rc = pu::launch("rfft_rows_kernel", rfft_rows_kernel<float, RfPlain, false>, rgrid, dim3(RF_THREADS), lds_rows,
+                                    s, nullptr, n, ld, mean, sh, w.tbl, w.tws, out, ld_spec, RfPlain{}))
+                return rc;
         }
-        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
-    } else {
-        const size_t lds_cols = ((size_t)RF_TILE + ((size_t)1 << sh.l1) / 2) * sizeof(float2);
-        const dim3 cgrid((unsigned)(vrows * cgroups)), rgrid((unsigned)(vrows * groups));
-        if (dtype == PU_F32) {
-            RF_ATTR((rfft_cols_kernel<float, MAP>), lds_cols);
-            hipLaunchKernelGGL((rfft_cols_kernel<float, MAP>), cgrid, dim3(RF_THREADS), lds_cols, s,
-                               static_cast<const float *>(x), n, ld, mean, sh, tbl, tws, map);
-        } else {
-            RF_ATTR((rfft_cols_kernel<double, MAP>), lds_cols);
-            hipLaunchKernelGGL((rfft_cols_kernel<double, MAP>), cgrid, dim3(RF_THREADS), lds_cols, s,
-                               static_cast<const double *>(x), n, ld, mean, sh, tbl, tws, map);
-        }
-        if (int rc = pu::launch_check("rfft_cols_kernel")) return rc;
-        // the second pass reads the workspace, never x: one instance serves both entry points
-        RF_ATTR((rfft_rows_kernel<float, RfPlain, false>), lds_rows);
-        hipLaunchKernelGGL((rfft_rows_kernel<float, RfPlain, false>), rgrid, dim3(RF_THREADS), lds_rows, s,
-                           static_cast<const float *>(nullptr), n, ld, mean, sh, tbl, tws, out, ld_spec, RfPlain{});
-        if (int rc = pu::launch_check("rfft_rows_kernel")) return rc;
-    }
-#undef RF_ATTR
-    hipLaunchKernelGGL(rfft_split_kernel, dim3((unsigned)((m / 2 + 1 + 255) / 256), (unsigned)vrows), dim3(256), 0, s, out,
-                       ld_spec, m, tbl);
-    return pu::launch_check("rfft_split_kernel");
+        return pu::launch("rfft_split_kernel", rfft_split_kernel, dim3((unsigned)((m / 2 + 1 + 255) / 256), (unsigned)vrows),
+                          dim3(256), 0, s, out, ld_spec, m, w.tbl);
+    });
 }
 
 // rows and nacc of an acceleration call: both in [0, 2^31), so that their product is an int64
@@ -358,11 +349,9 @@ extern "C" {
 size_t pu_rfft_workspace_bytes(int64_t rows, int64_t nfft)
 {
     if (rows <= 0 || !rf_valid_nfft(nfft)) return 0;
-    const RfShape sh = rf_shape(nfft);
-    const size_t tbl = rf_up256((size_t)(nfft / 2) * sizeof(float2));
-    if (sh.l1 == 0) return tbl;
-    if ((size_t)rows > (SIZE_MAX - tbl) / ((size_t)(nfft / 2) * sizeof(float2))) return SIZE_MAX;
-    return tbl + (size_t)rows * (size_t)(nfft / 2) * sizeof(float2);
+    const size_t half = (size_t)(nfft / 2) * sizeof(float2);
+    if (rf_shape(nfft).l1 && (size_t)rows > (SIZE_MAX - pu::up256(half)) / half) return SIZE_MAX;
+    return rf_carve(pu::Carver(), rows, nfft).bytes;
 }
 
 int pu_rfft(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *mean, int64_t nfft, void *spec,
@@ -395,30 +384,23 @@ int pu_rfft_accel(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld,
 int pu_resample_accel(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *afac, int64_t nacc,
                       void *out, int64_t ld_out, void *stream)
 {
-    if (dtype != PU_F32 && dtype != PU_F64) {
-        pu::set_error("pu_resample_accel: unsupported dtype %d (a dedispersed series is float32 or float64)", dtype);
-        return PU_EUNSUPPORTED;
-    }
-    PU_REQUIRE(rf_valid_trials(rows, nacc) && n >= 0 && n <= ((int64_t)1 << 24),
-               "pu_resample_accel: bad size (rows %lld, nacc %lld, n %lld; n <= 2^24)", (long long)rows, (long long)nacc,
-               (long long)n);
-    PU_REQUIRE(ld >= n && ld_out >= n, "pu_resample_accel: leading dimension too small (ld %lld or ld_out %lld < n %lld)",
-               (long long)ld, (long long)ld_out, (long long)n);
-    const int64_t vrows = rows * nacc;
-    if (vrows == 0 || n == 0) return PU_OK;
-    PU_REQUIRE(x && afac && out && x != out, "pu_resample_accel: null pointer, or out is x (not in place)");
-    const size_t es = pu::elem_size(dtype);
-    PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % es == 0 && reinterpret_cast<uintptr_t>(out) % es == 0 &&
-                   reinterpret_cast<uintptr_t>(afac) % 8 == 0,
-               "pu_resample_accel: x, out or afac is not aligned to its element type");
-    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(vrows < 65535 ? vrows : 65535));
-    if (dtype == PU_F32)
-        hipLaunchKernelGGL(resample_accel_kernel<float>, grid, dim3(256), 0, pu::as_stream(stream),
-                           static_cast<const float *>(x), rows, n, ld, afac, vrows, static_cast<float *>(out), ld_out);
-    else
-        hipLaunchKernelGGL(resample_accel_kernel<double>, grid, dim3(256), 0, pu::as_stream(stream),
-                           static_cast<const double *>(x), rows, n, ld, afac, vrows, static_cast<double *>(out), ld_out);
-    return pu::launch_check("resample_accel_kernel");
+    return pu::with_dtype<float, double>("pu_resample_accel", dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        PU_REQUIRE(rf_valid_trials(rows, nacc) && n >= 0 && n <= ((int64_t)1 << 24),
+                   "pu_resample_accel: bad size (rows %lld, nacc %lld, n %lld; n <= 2^24)", (long long)rows, (long long)nacc,
+                   (long long)n);
+        PU_REQUIRE(ld >= n && ld_out >= n, "pu_resample_accel: leading dimension too small (ld %lld or ld_out %lld < n %lld)",
+                   (long long)ld, (long long)ld_out, (long long)n);
+        const int64_t vrows = rows * nacc;
+        if (vrows == 0 || n == 0) return PU_OK;
+        PU_REQUIRE(x && afac && out && x != out, "pu_resample_accel: null pointer, or out is x (not in place)");
+        PU_REQUIRE(reinterpret_cast<uintptr_t>(x) % sizeof(T) == 0 && reinterpret_cast<uintptr_t>(out) % sizeof(T) == 0 &&
+                       reinterpret_cast<uintptr_t>(afac) % 8 == 0,
+                   "pu_resample_accel: x, out or afac is not aligned to its element type");
+        const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(vrows < 65535 ? vrows : 65535));
+        return pu::launch("resample_accel_kernel", resample_accel_kernel<T>, grid, dim3(256), 0, pu::as_stream(stream),
+                          static_cast<const T *>(x), rows, n, ld, afac, vrows, static_cast<T *>(out), ld_out);
+    });
 }
 
 }  // extern "C"

@@ -204,7 +204,20 @@ hs_search_kernel(const float *__restrict__ norm, int64_t nb, int64_t ld, int nle
     }
 }
 
-size_t hs_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// pu_harmonic_search's workspace: a count (then offset) per (row, level, tile), then the total
+struct HsWs {
+    int64_t *blk, *total;
+    size_t bytes;
+};
+
+HsWs hs_carve(pu::Carver c, int64_t slots)
+{
+    HsWs w;
+    w.blk = c.take<int64_t>((size_t)slots * 8);
+    w.total = c.take<int64_t>(256);
+    w.bytes = c.used();
+    return w;
+}
 
 }  // namespace
 
@@ -227,16 +240,14 @@ int pu_spectrum_normalize(const void *spec, int64_t rows, int64_t nb, int64_t ld
     int lb = 0;
     while (((int64_t)1 << lb) < block) ++lb;
     const dim3 grid((unsigned)((nb + SN_TILE - 1) / SN_TILE), (unsigned)rows);
-    hipLaunchKernelGGL(spec_normalize_kernel, grid, dim3(256), 0, pu::as_stream(stream),
-                       static_cast<const float2 *>(spec), ld_spec, nb, lb, out, ld_out);
-    return pu::launch_check("spec_normalize_kernel");
+    return pu::launch("spec_normalize_kernel", spec_normalize_kernel, grid, dim3(256), 0, pu::as_stream(stream),
+                      static_cast<const float2 *>(spec), ld_spec, nb, lb, out, ld_out);
 }
 
 size_t pu_harmonic_search_workspace_bytes(int64_t rows, int64_t nb, int64_t nlev)
 {
     if (rows <= 0 || nb <= 0 || nlev <= 0) return 0;
-    const int64_t ntile = (nb + HS_TILE - 1) / HS_TILE;
-    return hs_up256((size_t)rows * (size_t)nlev * (size_t)ntile * 8) + 256;
+    return hs_carve(pu::Carver(), rows * nlev * ((nb + HS_TILE - 1) / HS_TILE)).bytes;
 }
 
 int pu_harmonic_search(const float *norm, int64_t rows, int64_t nb, int64_t ld, int64_t nlev, float *sums,
@@ -256,30 +267,22 @@ int pu_harmonic_search(const float *norm, int64_t rows, int64_t nb, int64_t ld, 
     *count = 0;
     if (rows == 0) return PU_OK;
     PU_REQUIRE(norm, "pu_harmonic_search: null pointer");
-    const size_t need = pu_harmonic_search_workspace_bytes(rows, nb, nlev);
-    PU_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
-               "pu_harmonic_search: workspace of %zu bytes (256-byte aligned) needed, got %zu", need, workspace_bytes);
     HsLevels lv{};
     for (int l = 0; l < nlev; ++l) lv.thr[l] = thr[l], lv.kmin[l] = kmin[l], lv.kmax[l] = kmax[l];
     const int64_t ntile = (nb + HS_TILE - 1) / HS_TILE, slots = rows * nlev * ntile;
-    int64_t *blk = static_cast<int64_t *>(workspace);
-    int64_t *total = reinterpret_cast<int64_t *>(static_cast<unsigned char *>(workspace) + hs_up256((size_t)slots * 8));
+    const HsWs w = hs_carve(pu::Carver(workspace), slots);
+    if (int rc = pu::check_workspace("pu_harmonic_search", workspace, workspace_bytes, w.bytes, 256)) return rc;
     hipStream_t s = pu::as_stream(stream);
     const dim3 grid((unsigned)ntile, (unsigned)rows);
-    hipLaunchKernelGGL(hs_search_kernel<false>, grid, dim3(256), 0, s, norm, nb, ld, (int)nlev, sums, ld_level, ld_row, lv,
-                       blk, ntile, total, cands, cap);
-    int rc = pu::launch_check("hs_search_kernel<count>");
-    if (!rc) {
-        hipLaunchKernelGGL(hs_scan_kernel, dim3(1), dim3(1024), 0, s, blk, slots, total);
-        rc = pu::launch_check("hs_scan_kernel");
-    }
-    if (!rc && cap > 0) {
-        hipLaunchKernelGGL(hs_search_kernel<true>, grid, dim3(256), 0, s, norm, nb, ld, (int)nlev, nullptr, ld_level,
-                           ld_row, lv, blk, ntile, total, cands, cap);
-        rc = pu::launch_check("hs_search_kernel<emit>");
-    }
+    // run on after an error, then synchronise, then report the first one
+    int rc = pu::launch("hs_search_kernel<count>", hs_search_kernel<false>, grid, dim3(256), 0, s, norm, nb, ld, (int)nlev,
+                        sums, ld_level, ld_row, lv, w.blk, ntile, w.total, cands, cap);
+    if (!rc) rc = pu::launch("hs_scan_kernel", hs_scan_kernel, dim3(1), dim3(1024), 0, s, w.blk, slots, w.total);
+    if (!rc && cap > 0)
+        rc = pu::launch("hs_search_kernel<emit>", hs_search_kernel<true>, grid, dim3(256), 0, s, norm, nb, ld, (int)nlev,
+                        nullptr, ld_level, ld_row, lv, w.blk, ntile, w.total, cands, cap);
     if (!rc)
-        rc = pu::hip_check(hipMemcpyAsync(count, total, sizeof(int64_t), hipMemcpyDeviceToHost, s),
+        rc = pu::hip_check(hipMemcpyAsync(count, w.total, sizeof(int64_t), hipMemcpyDeviceToHost, s),
                            "hipMemcpyAsync(candidate count)");
     const int rs = pu::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(harmonic search)");
     return rc ? rc : rs;

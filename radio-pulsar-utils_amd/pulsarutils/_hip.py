@@ -261,6 +261,36 @@ def to_device(a, allowed=(PU_U8, PU_F32, PU_F64), device=None):
     return x.contiguous()
 
 
+def workspace(nbytes, device, align=256):
+    """(tensor, pointer, size): ``nbytes`` of device memory for a library workspace, from an
+    ``align``-byte aligned address - the tensor that owns it, the ``c_void_p`` of the aligned
+    start and the bytes usable from there (at least ``nbytes``)."""
+    t = torch()
+    buf = t.empty(max(16, int(nbytes)) + align, dtype=t.uint8, device=device)
+    off = (-buf.data_ptr()) % align
+    return buf, ctypes.c_void_p(buf.data_ptr() + off), buf.numel() - off
+
+
+def row_stride(x):
+    """The leading dimension of 2-D row-major ``x`` as the library wants it: the row stride, but
+    for a single row (whose stride torch leaves arbitrary) at least the row's length."""
+    return x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+
+
+def as_rows(a, what, allowed):
+    """(2-D device tensor of an ``allowed`` dtype, the input was 1-D, the input was numpy): a
+    1-D input is one row; ``what`` is the ``ValueError``'s text for any other shape."""
+    t = require_gpu()
+    as_numpy = not isinstance(a, t.Tensor)
+    x = to_device(a, allowed=allowed)
+    one_d = x.dim() == 1
+    if one_d:
+        x = x.reshape(1, -1)
+    if x.dim() != 2:
+        raise ValueError(what)
+    return x, one_d, as_numpy
+
+
 def _plan_inputs(nchan, shifts, group, shape, lds_budget_kb, u8_dma, dt_major, slot16):
     """The shift table as the library reads it and ``pu_plan_opts`` from ``Plan``'s keywords."""
     sh = np.ascontiguousarray(shifts, dtype=np.int64)
@@ -603,10 +633,9 @@ def series_stats(series, stream=None):
         return out
     per = max(1, min(rows, (1 << 30) // max(1, 12 * n)))
     wsb = lib().pu_series_stats_workspace_bytes(per, n)
-    ws = t.empty(wsb + 256, dtype=t.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws, wp, _ = workspace(wsb, dev)
     check(lib().pu_series_stats(ptr(series), rows, n, series.stride(0), None, ptr(out[0]), ptr(out[1]), ptr(out[2]),
-                                ptr(out[3]), ctypes.c_void_p(ws.data_ptr() + off), wsb, stream_ptr(stream)),
+                                ptr(out[3]), wp, wsb, stream_ptr(stream)),
           "pu_series_stats")
     return out
 
@@ -631,14 +660,13 @@ def series_events(series, threshold, index=None, stream=None):
         idx = t.from_numpy(ih).to(dev)
     per = max(1, min(rows, (1 << 30) // max(1, 16 * n)))
     wsb = lib().pu_series_events_workspace_bytes(per, n)
-    ws = t.empty(wsb + 256, dtype=t.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws, wp, _ = workspace(wsb, dev)
     cap = max(256, 8 * rows)
     count = ctypes.c_int64(0)
     while True:
         buf = t.empty(cap * EVENT_DTYPE.itemsize, dtype=t.uint8, device=dev)
         check(lib().pu_series_events(ptr(series), rows, n, series.stride(0), ptr(idx), float(threshold), ptr(buf), cap,
-                                     ctypes.byref(count), ctypes.c_void_p(ws.data_ptr() + off), wsb,
+                                     ctypes.byref(count), wp, wsb,
                                      stream_ptr(stream)), "pu_series_events")
         if count.value <= cap:
             break

@@ -167,9 +167,8 @@ def median_device(x):
     t = _hip.torch()
     lib = _hip.lib()
     out = t.empty(1, dtype=t.float64, device=x.device)
-    ws = t.empty(lib.pu_median_workspace_bytes(), dtype=t.uint8, device=x.device)
-    _hip.check(lib.pu_median(_hip.ptr(x), x.numel(), _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
-               "pu_median")
+    ws, wp, wsb = _hip.workspace(lib.pu_median_workspace_bytes(), x.device)
+    _hip.check(lib.pu_median(_hip.ptr(x), x.numel(), _hip.ptr(out), wp, wsb, _hip.stream_ptr()), "pu_median")
     return out
 
 
@@ -370,14 +369,11 @@ def light_curve_factor(lc, weights, radius, median_out=None):
     t = _hip.torch()
     lib = _hip.lib()
     n = lc.numel()
-    nbytes = lib.pu_lc_factor_workspace_bytes(n)
-    # the caching allocator's blocks are stream-ordered and 512-byte aligned
-    buf = t.empty(nbytes, dtype=t.uint8, device=lc.device)
-    assert buf.data_ptr() % 256 == 0
+    buf, wp, wsb = _hip.workspace(lib.pu_lc_factor_workspace_bytes(n), lc.device)
     factor = t.empty(n, dtype=t.float64, device=lc.device)
     _hip.check(lib.pu_lc_factor(_hip.ptr(lc), n, _hip.ptr(weights), int(radius), _hip.ptr(factor),
-                                _hip.ptr(median_out) if median_out is not None else None, buf.data_ptr(),
-                                nbytes, _hip.stream_ptr()), "pu_lc_factor")
+                                _hip.ptr(median_out) if median_out is not None else None, wp, wsb,
+                                _hip.stream_ptr()), "pu_lc_factor")
     return factor
 
 
@@ -454,10 +450,10 @@ def renormalize_device(x, badchans_mask=None, baseline_window=101, cut_outliers=
     if cut_outliers and n >= 64:
         # device path (pu_cut_outliers): certified decisions, and the reference's own
         # arithmetic on the device for the rare ambiguous / NaN case - no host round trip
-        ws = t.empty(lib.pu_cut_outliers_workspace_bytes(n), dtype=t.uint8, device=dev)
+        ws, wp, wsb = _hip.workspace(lib.pu_cut_outliers_workspace_bytes(n), dev)
         mask = t.empty(n, dtype=t.uint8, device=dev)
         _hip.check(lib.pu_cut_outliers(_hip.ptr(col), n, _hip.ptr(out), nchan, out.stride(0), _hip.ptr(mask),
-                                       _hip.ptr(ws), ws.numel(), s), "pu_cut_outliers")
+                                       wp, wsb, s), "pu_cut_outliers")
         return out, mask.view(t.bool)
     if cut_outliers:
         # n < 64: scipy on the host, as the reference does

@@ -47,15 +47,12 @@ def fold_bins(nsamples, pulse_freq, sample_time, nbin, ph0=0.0, first_sample=0):
 
 def _fold_device(x, dphase, nbin, ph0, first_sample, sums, counts):
     """pu_fold of a 2-D row-major device tensor into device ``sums`` / ``counts``."""
-    t = _hip.torch()
     lib = _hip.lib()
     nchan, n = x.shape
-    ld = x.stride(0) if nchan > 1 else max(x.stride(0), n)
-    wsb = lib.pu_fold_workspace_bytes(nchan, n, nbin)
-    ws = t.empty(max(16, wsb), dtype=t.uint8, device=x.device)
-    _hip.check(lib.pu_fold(_hip.ptr(x), _hip.dtype_code(x.dtype), nchan, n, ld, int(first_sample), float(ph0),
-                           float(dphase), int(nbin), _hip.ptr(sums), sums.stride(0), _hip.ptr(counts), _hip.ptr(ws),
-                           ws.numel(), _hip.stream_ptr()), "pu_fold")
+    ws, wp, wsb = _hip.workspace(lib.pu_fold_workspace_bytes(nchan, n, nbin), x.device)
+    _hip.check(lib.pu_fold(_hip.ptr(x), _hip.dtype_code(x.dtype), nchan, n, _hip.row_stride(x), int(first_sample),
+                           float(ph0), float(dphase), int(nbin), _hip.ptr(sums), sums.stride(0), _hip.ptr(counts), wp,
+                           wsb, _hip.stream_ptr()), "pu_fold")
 
 
 def fold(data, pulse_freq, sample_time, nbin, ph0=0.0, first_sample=0, out=None):
@@ -70,13 +67,8 @@ def fold(data, pulse_freq, sample_time, nbin, ph0=0.0, first_sample=0, out=None)
     float64.  Exact for uint8 (and for integer-valued input below 2^53); reproducible bit for
     bit otherwise (no floating-point atomics)."""
     t = _hip.require_gpu()
-    as_numpy = not isinstance(data, t.Tensor)
-    x = _hip.to_device(data)
-    one_d = x.dim() == 1
-    if one_d:
-        x = x.reshape(1, -1)
-    if x.dim() != 2:
-        raise ValueError("fold: data must be (nchan, nsamples) or 1-D")
+    x, one_d, as_numpy = _hip.as_rows(data, "fold: data must be (nchan, nsamples) or 1-D",
+                                      (_hip.PU_U8, _hip.PU_F32, _hip.PU_F64))
     nbin = int(nbin)
     if nbin < 1:
         raise ValueError("fold: nbin must be >= 1")
@@ -174,26 +166,15 @@ def _h_test_device(prof, nmax, want_zs):
     h = t.empty(rows, dtype=t.float64, device=prof.device)
     m = t.empty(rows, dtype=t.int32, device=prof.device)
     zs = t.empty((rows, max(nmax, 1)), dtype=t.float64, device=prof.device) if want_zs else None
-    wsb = lib.pu_h_test_workspace_bytes(rows, n, nmax)
-    ws = t.empty(max(16, wsb), dtype=t.uint8, device=prof.device)  # (allocator blocks are 512-byte aligned)
-    ld = prof.stride(0) if rows > 1 else max(prof.stride(0), n)
-    _hip.check(lib.pu_h_test(_hip.ptr(prof), rows, n, ld, nmax, _hip.ptr(h), _hip.ptr(m), _hip.ptr(zs),
-                             zs.stride(0) if zs is not None else 0, _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
-               "pu_h_test")
+    ws, wp, wsb = _hip.workspace(lib.pu_h_test_workspace_bytes(rows, n, nmax), prof.device)
+    _hip.check(lib.pu_h_test(_hip.ptr(prof), rows, n, _hip.row_stride(prof), nmax, _hip.ptr(h), _hip.ptr(m), _hip.ptr(zs),
+                             zs.stride(0) if zs is not None else 0, wp, wsb, _hip.stream_ptr()), "pu_h_test")
     return h, m, zs
 
 
 def _profiles(profiles):
     """(float64 2-D device tensor, the input was 1-D, the input was numpy)."""
-    t = _hip.require_gpu()
-    as_numpy = not isinstance(profiles, t.Tensor)
-    x = _hip.to_device(profiles, allowed=(_hip.PU_F64,))
-    one_d = x.dim() == 1
-    if one_d:
-        x = x.reshape(1, -1)
-    if x.dim() != 2:
-        raise ValueError("profiles must be 1-D or (rows, n)")
-    return x, one_d, as_numpy
+    return _hip.as_rows(profiles, "profiles must be 1-D or (rows, n)", (_hip.PU_F64,))
 
 
 def z_n_all(profiles, nmax=20):
@@ -290,15 +271,7 @@ _TRIALS_WS_BYTES = 1 << 30  # pu_fold_trials' partials per call: longer trial li
 
 def _series(series, what):
     """(float32 / float64 2-D device tensor, the input was 1-D, the input was numpy)."""
-    t = _hip.require_gpu()
-    as_numpy = not isinstance(series, t.Tensor)
-    x = _hip.to_device(series, allowed=(_hip.PU_F32, _hip.PU_F64))
-    one_d = x.dim() == 1
-    if one_d:
-        x = x.reshape(1, -1)
-    if x.dim() != 2:
-        raise ValueError(f"{what}: series must be (rows, nsamples) or 1-D")
-    return x, one_d, as_numpy
+    return _hip.as_rows(series, f"{what}: series must be (rows, nsamples) or 1-D", (_hip.PU_F32, _hip.PU_F64))
 
 
 def _fold_trials_device(x, dphase, phase0, nbin, first_sample, sums, counts):
@@ -306,22 +279,21 @@ def _fold_trials_device(x, dphase, phase0, nbin, first_sample, sums, counts):
     ``counts`` (F, nbin); ``dphase``, ``phase0``: float64 device tensors (F,).  The trial list
     goes in batches whose partials stay under ``_TRIALS_WS_BYTES`` (a trial's bits do not
     depend on the batch it is in)."""
-    t = _hip.torch()
     lib = _hip.lib()
     rows, n = x.shape
     ntrials = dphase.numel()
     if rows == 0 or n == 0 or ntrials == 0:
         return
-    ld = x.stride(0) if rows > 1 else max(x.stride(0), n)
+    ld = _hip.row_stride(x)
     per_trial = max(1, lib.pu_fold_trials_workspace_bytes(rows, n, 1, nbin))
     batch = max(1, min(ntrials, _TRIALS_WS_BYTES // per_trial))
-    ws = t.empty(max(16, lib.pu_fold_trials_workspace_bytes(rows, n, batch, nbin)), dtype=t.uint8, device=x.device)
+    ws, wp, wsb = _hip.workspace(lib.pu_fold_trials_workspace_bytes(rows, n, batch, nbin), x.device)
     for k0 in range(0, ntrials, batch):
         nk = min(batch, ntrials - k0)
         _hip.check(lib.pu_fold_trials(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, ld, int(first_sample),
                                       _hip.ptr(phase0[k0:]), _hip.ptr(dphase[k0:]), nk, int(nbin),
                                       _hip.ptr(sums[:, k0:]), sums.stride(1), sums.stride(0), _hip.ptr(counts[k0:]),
-                                      _hip.ptr(ws), ws.numel(), _hip.stream_ptr()), "pu_fold_trials")
+                                      wp, wsb, _hip.stream_ptr()), "pu_fold_trials")
 
 
 def _trial_phases(freqs, sample_time, ph0, device):

@@ -287,14 +287,8 @@ def acceleration_grid(amax, tobs, ftop, drift_bins=1.0):
 
 def _series(series, what):
     """(float32 / float64 2-D device tensor, the input was 1-D, the input was numpy)."""
-    t = _hip.require_gpu()
-    as_numpy = not isinstance(series, t.Tensor)
-    x = _hip.to_device(series, allowed=(_hip.PU_F32, _hip.PU_F64))
-    one_d = x.dim() == 1
-    if one_d:
-        x = x.reshape(1, -1)
-    if x.dim() != 2:
-        raise ValueError(f"{what}: series must be (rows, nsamples) or 1-D")
+    x, one_d, as_numpy = _hip.as_rows(series, f"{what}: series must be (rows, nsamples) or 1-D",
+                                      (_hip.PU_F32, _hip.PU_F64))
     if x.shape[1] < 1:
         raise ValueError(f"{what}: an empty series")
     return x, one_d, as_numpy
@@ -316,12 +310,7 @@ def _check_block(block, nb):
     return block
 
 
-def _aligned(nbytes, device):
-    """(tensor, pointer, size): ``nbytes`` of device memory from a 256-byte aligned address."""
-    t = _hip.torch()
-    buf = t.empty(max(16, int(nbytes)) + 256, dtype=t.uint8, device=device)
-    off = (-buf.data_ptr()) % 256
-    return buf, ctypes.c_void_p(buf.data_ptr() + off), buf.numel() - off
+_aligned = _hip.workspace  # the name callers of this module knew it by
 
 
 def _rows_per_call(rows, nfft):
@@ -341,13 +330,13 @@ def _rfft_device(x, nfft, mean=None):
         return spec
     if mean is None:
         mean = _chunk_row_sums(x, 3) / float(n)
-    ld = x.stride(0) if rows > 1 else max(x.stride(0), n)
     per = _rows_per_call(rows, nfft)
-    ws, wp, wsb = _aligned(lib.pu_rfft_workspace_bytes(per, nfft), x.device)
+    ws, wp, wsb = _hip.workspace(lib.pu_rfft_workspace_bytes(per, nfft), x.device)
     for r0 in range(0, rows, per):
         m = min(per, rows - r0)
-        _hip.check(lib.pu_rfft(_hip.ptr(x[r0:]), _hip.dtype_code(x.dtype), m, n, ld, _hip.ptr(mean[r0:]), nfft,
-                               _hip.ptr(spec[r0:]), spec.stride(0), wp, wsb, _hip.stream_ptr()), "pu_rfft")
+        _hip.check(lib.pu_rfft(_hip.ptr(x[r0:]), _hip.dtype_code(x.dtype), m, n, _hip.row_stride(x),
+                               _hip.ptr(mean[r0:]), nfft, _hip.ptr(spec[r0:]), spec.stride(0), wp, wsb,
+                               _hip.stream_ptr()), "pu_rfft")
     return spec
 
 
@@ -379,11 +368,10 @@ def _harmonic_search_device(norm, nlev, thr, kmin, kmax, sums=None, cap=0):
     count = ctypes.c_int64(0)
     if rows == 0:
         return np.zeros(0, _hip.SPEC_CAND_DTYPE), 0
-    ws, wp, wsb = _aligned(lib.pu_harmonic_search_workspace_bytes(rows, nb, nlev), norm.device)
+    ws, wp, wsb = _hip.workspace(lib.pu_harmonic_search_workspace_bytes(rows, nb, nlev), norm.device)
     cap = int(cap)
     buf = t.empty(max(1, cap) * _hip.SPEC_CAND_DTYPE.itemsize, dtype=t.uint8, device=norm.device) if cap > 0 else None
-    ld = norm.stride(0) if rows > 1 else max(norm.stride(0), nb)
-    _hip.check(lib.pu_harmonic_search(_hip.ptr(norm), rows, nb, ld, nlev, _hip.ptr(sums),
+    _hip.check(lib.pu_harmonic_search(_hip.ptr(norm), rows, nb, _hip.row_stride(norm), nlev, _hip.ptr(sums),
                                       sums.stride(0) if sums is not None else 0,
                                       sums.stride(1) if sums is not None else 0,
                                       thr.ctypes.data_as(ctypes.c_void_p), kmin.ctypes.data_as(ctypes.c_void_p),
@@ -425,15 +413,11 @@ def harmonic_sums(norm, nharm=16):
     ``(nlev, rows, nb)`` (``(nlev, nb)`` for a 1-D spectrum)."""
     nlev = _nlev(nharm)
     t = _hip.require_gpu()
-    as_numpy = not isinstance(norm, t.Tensor)
-    x = _hip.to_device(norm, allowed=(_hip.PU_F32,))
+    x, one_d, as_numpy = _hip.as_rows(norm, "harmonic_sums: a normalised spectrum (rows, nb) or 1-D", (_hip.PU_F32,))
+    if x.shape[1] < 1:
+        raise ValueError("harmonic_sums: a normalised spectrum (rows, nb) or 1-D")
     if x.dtype != t.float32:
         x = x.to(t.float32)
-    one_d = x.dim() == 1
-    if one_d:
-        x = x.reshape(1, -1)
-    if x.dim() != 2 or x.shape[1] < 1:
-        raise ValueError("harmonic_sums: a normalised spectrum (rows, nb) or 1-D")
     rows, nb = x.shape
     sums = t.empty((nlev, rows, nb), dtype=t.float32, device=x.device)
     never = np.full(nlev, np.inf, np.float32)
@@ -548,9 +532,9 @@ def _resample_device(x, af):
     rows, n = x.shape
     nacc = af.numel()
     out = t.empty((nacc, rows, n), dtype=x.dtype, device=x.device)
-    ld = x.stride(0) if rows > 1 else max(x.stride(0), n)
-    _hip.check(_hip.lib().pu_resample_accel(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, ld, _hip.ptr(af), nacc,
-                                            _hip.ptr(out), n, _hip.stream_ptr()), "pu_resample_accel")
+    _hip.check(_hip.lib().pu_resample_accel(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, _hip.row_stride(x),
+                                            _hip.ptr(af), nacc, _hip.ptr(out), n, _hip.stream_ptr()),
+               "pu_resample_accel")
     return out
 
 
@@ -567,22 +551,22 @@ def _accel_batches(rows, nacc, nfft):
 
 def _rfft_accel_device(x, af, mean, nfft, ws, spec=None):
     """pu_rfft_accel of one batch: ``x`` (rows, n), ``af`` (nacc,), ``mean`` (rows,) -> complex64
-    (nacc * rows, nfft / 2 + 1), pair ``a * rows + r``.  ``ws``: :func:`_aligned` workspace."""
+    (nacc * rows, nfft / 2 + 1), pair ``a * rows + r``.  ``ws``: :func:`_hip.workspace` triple."""
     t = _hip.torch()
     rows, n = x.shape
     nacc = af.numel()
     if spec is None:
         spec = t.empty((nacc * rows, nfft // 2 + 1), dtype=t.complex64, device=x.device)
-    ld = x.stride(0) if rows > 1 else max(x.stride(0), n)
-    _hip.check(_hip.lib().pu_rfft_accel(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, ld, _hip.ptr(mean), _hip.ptr(af),
-                                        nacc, nfft, _hip.ptr(spec), spec.stride(0), ws[1], ws[2], _hip.stream_ptr()),
+    _hip.check(_hip.lib().pu_rfft_accel(_hip.ptr(x), _hip.dtype_code(x.dtype), rows, n, _hip.row_stride(x),
+                                        _hip.ptr(mean), _hip.ptr(af), nacc, nfft, _hip.ptr(spec), spec.stride(0), ws[1],
+                                        ws[2], _hip.stream_ptr()),
                "pu_rfft_accel")
     return spec
 
 
 def _accel_workspace(batches, nfft, device):
     lib = _hip.lib()
-    return _aligned(max(lib.pu_rfft_accel_workspace_bytes(r1 - r0, a1 - a0, nfft) for a0, a1, r0, r1 in batches), device)
+    return _hip.workspace(max(lib.pu_rfft_accel_workspace_bytes(r1 - r0, a1 - a0, nfft) for a0, a1, r0, r1 in batches), device)
 
 
 def resample(series, accel, sample_time):

@@ -309,10 +309,8 @@ def transpose_device(src):
         raise ValueError("transpose_device: a 2-D CUDA tensor with unit column stride")
     rows, cols = src.shape
     out = t.empty((cols, rows), dtype=src.dtype, device=src.device)
-    # a single row's stride is arbitrary in torch: any value >= the row's length will do
-    ld_src = src.stride(0) if rows > 1 else max(src.stride(0), cols)
-    _hip.check(_hip.lib().pu_transpose(_hip.ptr(src), src.element_size(), rows, cols, ld_src, _hip.ptr(out),
-                                       rows, _hip.stream_ptr()), "pu_transpose")
+    _hip.check(_hip.lib().pu_transpose(_hip.ptr(src), src.element_size(), rows, cols, _hip.row_stride(src),
+                                       _hip.ptr(out), rows, _hip.stream_ptr()), "pu_transpose")
     return out
 
 
@@ -333,10 +331,8 @@ def unpack_transpose_device(src, nbits, nchans):
     out = t.empty((nchans, nsamps), dtype=t.uint8, device=src.device)
     if nbits in _PACKED and out.numel() == 0:
         return out  # (an empty tensor has no pointer to pass)
-    # a single row's stride is arbitrary in torch: any value >= the row's bytes will do
-    ld_src = src.stride(0) if nsamps > 1 else max(src.stride(0), src.shape[1])
-    _hip.check(_hip.lib().pu_unpack_transpose(_hip.ptr(src), nbits, nsamps, nchans, ld_src, _hip.ptr(out),
-                                              nsamps, _hip.stream_ptr()), "pu_unpack_transpose")
+    _hip.check(_hip.lib().pu_unpack_transpose(_hip.ptr(src), nbits, nsamps, nchans, _hip.row_stride(src),
+                                              _hip.ptr(out), nsamps, _hip.stream_ptr()), "pu_unpack_transpose")
     return out
 
 
@@ -380,10 +376,8 @@ def quantize_pack_device(x, nbits, scale=None, offset=None):
     valid = nbits == 32 or (nbits in _PACKED + (8,) and nchans * nbits % 8 == 0)
     if valid and (scale is None) == (offset is None) and x.numel() == 0:
         return out  # (an empty tensor has no pointer to pass)
-    # a single row's stride is arbitrary in torch: any value >= the row's length will do
-    ld_src = x.stride(0) if nchans > 1 else max(x.stride(0), nsamps)
-    _hip.check(_hip.lib().pu_quantize_pack_transpose(_hip.ptr(x), code, nchans, nsamps, ld_src, _hip.ptr(scale),
-                                                     _hip.ptr(offset), nbits, _hip.ptr(out),
+    _hip.check(_hip.lib().pu_quantize_pack_transpose(_hip.ptr(x), code, nchans, nsamps, _hip.row_stride(x),
+                                                     _hip.ptr(scale), _hip.ptr(offset), nbits, _hip.ptr(out),
                                                      out.shape[1] * out.element_size(), _hip.stream_ptr()),
                "pu_quantize_pack_transpose")
     return out

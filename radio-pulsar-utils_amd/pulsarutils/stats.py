@@ -50,9 +50,9 @@ def _chunk_row_sums(block, mode):
     t = _hip.torch()
     nrows, n = block.shape
     out = t.empty(nrows, dtype=t.float64, device=block.device)
-    ws = t.empty(max(16, _hip.lib().pu_row_sums_workspace_bytes(nrows, n)), dtype=t.uint8, device=block.device)
+    ws, wp, wsb = _hip.workspace(_hip.lib().pu_row_sums_workspace_bytes(nrows, n), block.device)
     _hip.check(_hip.lib().pu_row_sums(_hip.ptr(block), _hip.dtype_code(block.dtype), nrows, n, block.stride(0), mode,
-                                      None, None, 0.0, _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
+                                      None, None, 0.0, _hip.ptr(out), wp, wsb, _hip.stream_ptr()),
                "pu_row_sums")
     return out
 

@@ -58,13 +58,13 @@ def gpu_rfft(hip, x, nfft, mean, afac=None, ld=None, ld_spec=None):
     lib = hip.lib()
     if afac is None:
         spec = torch.full((rows, ld_spec), float("nan"), dtype=torch.complex64, device="cuda")
-        ws, wp, wsb = pe._aligned(lib.pu_rfft_workspace_bytes(rows, nfft), xd.device)
+        ws, wp, wsb = hip.workspace(lib.pu_rfft_workspace_bytes(rows, nfft), xd.device)
         hip.check(lib.pu_rfft(hip.ptr(xd), hip.dtype_code(xd.dtype), rows, n, xd.stride(0), hip.ptr(md), nfft,
                               hip.ptr(spec), ld_spec, wp, wsb, hip.stream_ptr()), "pu_rfft")
     else:
         af = torch.from_numpy(np.asarray(afac, dtype=np.float64)).cuda()
         spec = torch.full((af.numel() * rows, ld_spec), float("nan"), dtype=torch.complex64, device="cuda")
-        ws, wp, wsb = pe._aligned(lib.pu_rfft_accel_workspace_bytes(rows, af.numel(), nfft), xd.device)
+        ws, wp, wsb = hip.workspace(lib.pu_rfft_accel_workspace_bytes(rows, af.numel(), nfft), xd.device)
         hip.check(lib.pu_rfft_accel(hip.ptr(xd), hip.dtype_code(xd.dtype), rows, n, xd.stride(0), hip.ptr(md), hip.ptr(af),
                                     af.numel(), nfft, hip.ptr(spec), ld_spec, wp, wsb, hip.stream_ptr()), "pu_rfft_accel")
     torch.cuda.synchronize()

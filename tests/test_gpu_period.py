@@ -49,6 +49,9 @@ CASES = [
     (1, SUB - 1, 130, 128, 12345), (1, SUB + 1, 70, 129, 0),
     (2, 1000, 300, 16, 0),
     (1, 1000, 70, 16, 2 ** 53 - 500),   # sample indices up to 2^53: the index is converted, not incremented
+    # nbin 72: the widest 256-trial tile, so both kernels' dynamic LDS is above 64 KiB (fold 160 KiB,
+    # counts 72 KiB: nbin 65 above does that for the incrementing instances, this for the converting ones)
+    (1, 1000, 70, 72, 2 ** 53 - 500),
 ]
 
 

@@ -45,7 +45,7 @@ def gpu_rfft(hip, x, nfft, mean=None, ld=None, ld_spec=None):
     spec = torch.full((rows, ld_spec), float("nan"), dtype=torch.complex64, device="cuda")
     md = None if mean is None else torch.from_numpy(np.asarray(mean, dtype=np.float64)).cuda()
     lib = hip.lib()
-    ws, wp, wsb = pe._aligned(lib.pu_rfft_workspace_bytes(rows, nfft), xd.device)
+    ws, wp, wsb = hip.workspace(lib.pu_rfft_workspace_bytes(rows, nfft), xd.device)
     hip.check(lib.pu_rfft(hip.ptr(xd), hip.dtype_code(xd.dtype), rows, n, xd.stride(0), hip.ptr(md), nfft, hip.ptr(spec),
                           ld_spec, wp, wsb, hip.stream_ptr()), "pu_rfft")
     torch.cuda.synchronize()
