@@ -48,7 +48,7 @@ from . import _hip
 
 NHARMS = (1, 2, 4, 8, 16, 32)
 MIN_NFFT, MAX_NFFT = 1 << 8, 1 << 24
-_FFT_WS_BYTES = 1 << 30  # pu_rfft's workspace per call: more rows go in batches
+_FFT_WS_BYTES = 1 << 30  # pu_rfft's workspace per call (its rows; the twiddle table on top): more rows go in batches
 _MAX_ROWS = 32768        # rows of one call (a launch's grid.y)
 
 

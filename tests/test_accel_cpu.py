@@ -87,6 +87,62 @@ def lib():
     return _hip.lib()
 
 
+# (rows, nacc, nfft, _FFT_WS_BYTES, _MAX_ROWS; None: the module's own).  A row of a four-step
+# length takes nfft / 2 x 8 bytes of workspace, a row of a one-pass length none.
+BATCH_CASES = [
+    (5, 5, 2 ** 14, None, None),                 # one call
+    (5, 5, 2 ** 14, 2 * 2 ** 16, None),          # room for 2 pairs < rows: one acceleration, rows 2 + 2 + 1
+    (5, 5, 2 ** 14, 10 * 2 ** 16, None),         # room for 10 pairs: whole accelerations, 2 per call
+    (5, 5, 2 ** 14, 7 * 2 ** 16 + 100, None),    # room for 7: one acceleration per call, 2 pairs of room unused
+    (5, 5, 2 ** 14, 5 * 2 ** 16, None),          # room for exactly the rows
+    (5, 5, 2 ** 14, 2 ** 16, None),              # one pair per call
+    (5, 5, 2 ** 14, None, 2),                    # the same shapes from the row limit
+    (5, 5, 2 ** 14, None, 12),
+    (3, 7, 256, None, 4),                        # a one-pass length: the row limit alone
+    (1, 9, 2 ** 20, 4 * 2 ** 22, None),          # one row: 4 accelerations per call
+    (256, 300, 2 ** 20, None, None),             # the unpatched limits: 1 GiB is 256 rows of 2^20
+    (300, 3, 2 ** 20, None, None),               # ... and rows 256 + 44 per acceleration beyond
+    (3, 65535, 256, None, None),                 # the most trials: 10922 accelerations per call
+    (40000, 2, 2 ** 8, None, None),              # more rows than a call takes
+    (32768, 2, 2 ** 8, None, None),              # exactly as many
+    (32769, 1, 2 ** 8, None, None),
+]
+
+
+@pytest.mark.parametrize("rows, nacc, nfft, ws_bytes, max_rows", BATCH_CASES)
+def test_accel_batches_cover_every_pair_once_in_order(lib, monkeypatch, rows, nacc, nfft, ws_bytes, max_rows):
+    if ws_bytes is not None:
+        monkeypatch.setattr(pe, "_FFT_WS_BYTES", ws_bytes)
+    if max_rows is not None:
+        monkeypatch.setattr(pe, "_MAX_ROWS", max_rows)
+    per_row = lib.pu_rfft_workspace_bytes(2, nfft) - lib.pu_rfft_workspace_bytes(1, nfft)
+    assert per_row == (nfft // 2 * 8 if nfft > 2 ** 13 else 0) and per_row <= pe._FFT_WS_BYTES
+    batches = pe._accel_batches(rows, nacc, nfft)
+    pairs = []
+    for a0, a1, r0, r1 in batches:
+        assert 0 <= a0 < a1 <= nacc and 0 <= r0 < r1 <= rows
+        # whole rows at several accelerations, or rows of one
+        assert (r0, r1) == (0, rows) or a1 == a0 + 1
+        m = (a1 - a0) * (r1 - r0)
+        # what one call takes: the grid, the row limit of the stages after the transform, and the
+        # workspace the rows' columns may fill (the twiddle table of nfft / 2 entries comes on top)
+        assert m <= 65535 and m <= pe._MAX_ROWS and m * per_row <= pe._FFT_WS_BYTES
+        assert lib.pu_rfft_accel_workspace_bytes(r1 - r0, a1 - a0, nfft) <= pe._FFT_WS_BYTES + nfft // 2 * 8 + 256
+        pairs.append(np.add.outer(np.arange(a0, a1) * rows, np.arange(r0, r1)).ravel())
+    # every (a, r) once, in (a, r) order: the order of the candidate list
+    assert np.array_equal(np.concatenate(pairs), np.arange(nacc * rows))
+    # both branches are what they say
+    per = pe._rows_per_call(rows * nacc, nfft)
+    if rows <= per:
+        assert all(b[2:] == (0, rows) for b in batches) and len(batches) == -(-nacc // (per // rows))
+    else:
+        assert len(batches) == nacc * -(-rows // per)
+    # the row batches of periodicity_search under the same limits
+    per = pe._rows_per_call(rows, nfft)
+    assert 1 <= per <= min(rows, pe._MAX_ROWS) and per * per_row <= pe._FFT_WS_BYTES
+    assert per == rows or per == pe._MAX_ROWS or (per + 1) * per_row > pe._FFT_WS_BYTES
+
+
 def _msg(lib):
     return lib.pu_last_error().decode()
 
