@@ -700,6 +700,74 @@ int pu_harmonic_search(const float *norm, int64_t rows, int64_t nb, int64_t ld, 
                        const int64_t *kmax, pu_spec_cand *cands, int64_t cap, int64_t *count,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ fast folding (FFA) */
+
+/* The fast folding algorithm: all m trial periods between p and p + 1 bins of a series of m x p
+ * samples for n log2 m adds, and the boxcar matched-filter S/N of the folded profiles.  No
+ * reference counterpart; the definition is this project's own (tests/ffa_oracle.py restates it in
+ * numpy) and claims parity with no other package.
+ *
+ * rdiv(a, b) = (2a + b) / (2b) for non-negative integers (integer division): a / b rounded half up.
+ *
+ * Transform.  The input is m >= 1 rows of p >= 2 float32 bins, x[i][j] = series[i p + j]; F(x) has
+ * m rows.  For m = 1, F(x) = x.  Otherwise nh = m / 2 (integer), nt = m - nh, H = F(x[0 .. nh)),
+ * T = F(x[nh .. m)), and for s = 0 .. m - 1
+ *     h = rdiv(s (nh - 1), m - 1),   t = rdiv(s (nt - 1), m - 1),   b = s - t
+ *     F[s][j] = H[h][j] + T[t][(j + b) mod p]
+ * each add one float32 addition with the head operand on the left, nothing fused or reassociated:
+ * every output bit is fixed by (m, p) and the row's samples alone, and numpy reproduces it.  Row s
+ * folds at a period of p + s / (m - 1) bins (p for m = 1); row 0 is the plain fold; row m - 1
+ * shifts input row i by exactly i, the period of row 0 at base period p + 1.  In between, the
+ * shift the tree gives input row i in trial s is non-decreasing in i and within 3 bins of
+ * s i / (m - 1) (checked for m = 2 .. 1099, 2048, 4096, 4099: worst 2.96, worst per-trial rms
+ * 1.43, about 0.35 for powers of two, where the rule is the classic radix-2 FFA).
+ *
+ * S/N.  For the profile v = F[s] (float32), a width w with 1 <= w < p and the noise sigma[r] of the
+ * series (device float64 [rows]; NULL means 1):
+ *     T   = sum_j (double)v[j]
+ *     B_w = max over b = 0 .. p - 1 of sum_{i < w} (double)v[(b + i) mod p]
+ *     snr = (float)((B_w - w T / p) / (sqrt((double)m w (1 - (double)w / p)) sigma[r]))
+ *     peak = the lowest b whose computed sum attains the maximum
+ * The sums are float64 differences of float64 prefix sums (a wave scan per 64 bins).  Bound: with
+ * A = sum_j |v[j]|, every computed window sum and the computed T are within 4 p 2^-53 A of their
+ * exact values, so the numerator is within N = 8 p 2^-53 A of the exact one and
+ *     |snr - exact| <= N / (sqrt(m w (1 - w / p)) sigma[r]) + 2^-23 |exact|
+ * (the last term: the quotient's float64 roundings and the one rounding to float32, barring
+ * underflow), and the exact window sum at the reported peak is within N of the exact maximum.
+ * Integer-valued samples whose sums stay below 2^24 make every sum exact.  A non-finite sample
+ * gives unspecified snr and peak in the trials that read it and touches no other.
+ *
+ * pu_ffa.  x: device, rows series; samples 0 .. m p - 1 of each are read and nothing beyond, ld >=
+ * m p.  out (device, may be NULL): out[r ld_out_row + s p + j] = F[s][j]; only those m p elements
+ * of a row are written.  snr (device, may be NULL): snr[(r m + s) nwidths + k] = the S/N at width
+ * widths[k]; peak (device int32, optional, only with snr): the same layout.  widths: a HOST array of
+ * nwidths int32, validated here and passed to the kernel by value (no device copy, no
+ * synchronisation).  The bottom levels run in LDS, B = pu_ffa_describe's "block_rows" rows per
+ * workgroup; the others are one pass over the plane each.  With out == NULL the top level is
+ * formed inside the S/N kernel and never written (when the tree has a level above the LDS ones);
+ * snr and peak have the same bits either way.  workspace: pu_ffa_describe's "workspace_bytes",
+ * 256-byte aligned (none when out is given and m <= B).  Two equal calls give equal bits; a row's
+ * bits depend neither on rows nor on its position in the batch.
+ * PU_EINVAL: p < 2; m < 1; rows < 0; ld < m p; ld_out_row < m p (with out); both out and snr NULL;
+ * peak without snr; with snr, nwidths outside 1 .. 16, a NULL widths or a width outside 1 .. p - 1;
+ * a NULL x or a misaligned pointer; a workspace too small or not 256-byte aligned.
+ * PU_EUNSUPPORTED: p > 2048 (an LDS block is two buffers of B p floats, B >= 8, within 128 KiB);
+ * rows x m > 2^31 - 1 (the grid of one call: the caller batches rows).  PU_OK without a launch for
+ * rows == 0.  All checked before any HIP call; asynchronous on stream.
+ *
+ * pu_ffa_describe: host only, no HIP call; what pu_ffa would do for the same sizes (want_out: out
+ * != NULL; nwidths: 0 when snr == NULL).  Fills up to n of {depth = ceil(log2 m), lds_levels,
+ * block_rows (B: the largest power of two <= 256 with B p <= 16384, whatever m is), workspace_bytes,
+ * global_levels (depth - lds_levels), p_max, lds_bytes (of the LDS kernel's workgroup),
+ * traffic_bytes (what the level split moves through device memory: the LDS kernel reads the
+ * series and writes a plane, every level above reads one plane and writes one - none when the top
+ * level is fused -, an unfused S/N reads one; plus snr and peak)}.  Errors as pu_ffa's for rows,
+ * m, p; nwidths outside 0 .. 16 or nothing wanted: PU_EINVAL. */
+int pu_ffa_describe(int64_t rows, int64_t m, int64_t p, int64_t nwidths, int want_out, int64_t *info, int n);
+int pu_ffa(const float *x, int64_t rows, int64_t ld, int64_t m, int64_t p, float *out, int64_t ld_out_row,
+           const int32_t *widths, int64_t nwidths, const double *sigma, float *snr, int32_t *peak,
+           void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

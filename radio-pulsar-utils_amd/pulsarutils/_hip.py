@@ -96,6 +96,8 @@ SIGNATURES = {
     "pu_harmonic_search_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pu_harmonic_search": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz,
                                   _vp]),
+    "pu_ffa_describe": (_i32, [_i64, _i64, _i64, _i64, _i32, _vp, _i32]),
+    "pu_ffa": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pu_stream_create_cu_masked": (_i32, [_i32, ctypes.POINTER(_vp)]),
     "pu_stream_destroy": (_i32, [_vp]),
 }
