@@ -179,8 +179,8 @@ def _widths(widths, p):
 def _rows_per_call(rows, m, p, nwidths, want_out):
     def ws(r):
         return describe(r, m, p, nwidths, want_out)["workspace_bytes"]
-    per_row = max(1, ws(2) - ws(1))
-    return max(1, min(rows, _MAX_ROWS_M // m, _WS_BYTES // per_row))
+    per_row = ws(2) - ws(1)  # 0: the transform alone with every level in LDS, which no workspace limits
+    return max(1, min(rows, _MAX_ROWS_M // m, _WS_BYTES // per_row if per_row else rows))
 
 
 def _ffa_device(x, p, want_out, widths=None, sigma=None, want_peak=True):

@@ -1,5 +1,6 @@
 """The FFA's host side without a GPU: the search plan, trial periods and widths, what
-pu_ffa_describe reports, and every argument error of pu_ffa before any HIP call."""
+pu_ffa_describe reports, the rows the drivers give one call, and every argument error of pu_ffa
+before any HIP call."""
 import ctypes
 import math
 
@@ -95,6 +96,32 @@ def test_describe_is_consistent():
                 info = ffa.describe(rows, m, p, 10, False)
                 assert info["workspace_bytes"] >= last  # monotone in rows
                 last = info["workspace_bytes"]
+
+
+# all levels in LDS (no workspace with out); rows far below, just below and above 256 bytes; one, two
+# and three levels above the LDS ones
+@pytest.mark.parametrize("m, p", [(1, 2), (5, 2), (7, 3), (13, 5), (37, 50), (81, 100), (129, 256), (300, 5), (9, 2047),
+                                  (33, 2048)])
+@pytest.mark.parametrize("nw, want_out", [(0, True), (4, True), (4, False)])
+def test_rows_per_call_keeps_the_limits_and_is_maximal(monkeypatch, m, p, nw, want_out):
+    def ws(r):
+        return ffa.describe(r, m, p, nw, want_out)["workspace_bytes"]
+    glob = ffa.describe(1, m, p, nw, want_out)["global_levels"]
+    nbuf = (1 if glob >= 1 else 0) if want_out else (2 if glob >= 2 else 1)  # the planes a call carves (ffa.hip)
+    assert nbuf * m * p * 4 <= ws(1) <= nbuf * (m * p * 4 + 255)
+    if want_out and glob == 0:
+        assert ws(1) == ws(1000) == 0
+    for ws_limit in sorted({ws(1), ws(2), ws(3) + 100, ws(10) + 1, ws(300), 4 << 30}):  # (a row always fits)
+        for rows_m_limit in (m, 2 * m, 3 * m + 1, 100 * m + m // 2, (1 << 31) - 1):
+            monkeypatch.setattr(ffa, "_WS_BYTES", ws_limit)
+            monkeypatch.setattr(ffa, "_MAX_ROWS_M", rows_m_limit)
+            for rows in (1, 2, 3, 5, 64, 1000):
+                per = ffa._rows_per_call(rows, m, p, nw, want_out)
+                case = (rows, ws_limit, rows_m_limit, per)
+                assert 1 <= per <= rows, case
+                assert per * m <= rows_m_limit, case
+                assert ws(per) <= ws_limit + 256 * nbuf, case  # (one round-up per buffer)
+                assert per == rows or (per + 1) * m > rows_m_limit or ws(per + 1) > ws_limit, case
 
 
 def _call(x=4096, rows=1, ld=64, m=4, p=16, out=8192, ld_out=64, widths=(1, 2), nw=None, sigma=0, snr=12288, peak=0,

@@ -15,14 +15,16 @@ pytestmark = pytest.mark.gpu
 NAN32 = np.float32(np.nan)
 
 
-def run_ffa(dev, x, m, p, want_out=True, widths=None, sigma=None, want_peak=True, pad_in=7, pad_out=5):
+def run_ffa(dev, x, m, p, want_out=True, widths=None, sigma=None, want_peak=True, pad_in=7, pad_out=5, nan_rows=()):
     """pu_ffa through the C ABI on rows ``x`` (rows, m p) with ld > m p, ld_out_row > m p and NaN in
     the input padding, the out padding and the whole workspace; checks that the padding survives.
+    ``nan_rows``: rows whose samples hold a non-finite value, exempt from the "no NaN" asserts.
     Returns (out (rows, m, p) or None, snr, peak (rows, m, nw) or None)."""
     import torch
     x = np.ascontiguousarray(x, dtype=np.float32)
     rows, mp = x.shape
     assert mp == m * p
+    clean = np.setdiff1d(np.arange(rows), np.asarray(nan_rows, dtype=np.int64))
     nw = 0 if widths is None else len(widths)
     xin = np.full((rows, mp + pad_in), NAN32, np.float32)
     xin[:, :mp] = x
@@ -44,12 +46,12 @@ def run_ffa(dev, x, m, p, want_out=True, widths=None, sigma=None, want_peak=True
         o = out.cpu().numpy()
         assert np.isnan(o[:, mp:]).all(), "out padding written"
         res = o[:, :mp].reshape(rows, m, p)
-        assert not np.isnan(res).any(), "a NaN of the padding or the workspace reached out"
+        assert not np.isnan(res[clean]).any(), "a NaN of the padding or the workspace reached out"
     assert np.isnan(xd.cpu().numpy()[:, mp:]).all()
     s = snr.cpu().numpy() if nw else None
     k = peak.cpu().numpy() if peak is not None else None
     if nw:
-        assert not np.isnan(s).any(), "a NaN of the padding or the workspace reached snr"
+        assert not np.isnan(s[clean]).any(), "a NaN of the padding or the workspace reached snr"
         assert k is None or ((k >= 0) & (k < p)).all()
     return res, s, k
 
