@@ -6,6 +6,8 @@ Test infrastructure only.  Nothing here imports ``pulsarutils.pulses`` (the code
 series come from ``oracle.dedisperse`` / ``oracle.search(return_dedisp=True)``.
 tests/test_pulse_oracle.py pins ``series_events`` against the golden-pinned
 ``oracle.trial_stats``."""
+import functools
+
 import numpy as np
 
 import oracle
@@ -144,6 +146,76 @@ def spike(m):
     d = np.zeros(m)
     d[m // 2] = 100.0
     return d
+
+
+# ---- many rows: the count table of pu_series_events beyond one wave and one trip of its scan ----
+EV_BLOCK = 2048        # bins of one workgroup of the event stage (csrc/exact.hip, kEvBlock)
+SCAN_WAVE = 64 * 8     # entries one wave of event_scan_kernel takes per trip
+SCAN_TRIP = 1024 * 8   # entries of one trip
+MAX_BATCH = 32768      # rows of one batch at the most (the launches' grid.y)
+
+
+def event_blocks(n):
+    """Entries of the count table per row: one per EV_BLOCK bins of each window."""
+    return sum(((n >> k) + EV_BLOCK - 1) // EV_BLOCK for k in range(4))
+
+
+def many_rows(rows, n, seed):
+    """``rows`` series of N(0, 1) noise with +12 on about 8 % of the samples; every 17th row all
+    zero (std 0: no event) and a NaN in sample 0 of every 29th row from row 5 (no event)."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((rows, n))
+    x[rng.random((rows, n)) < 0.08] += 12.0
+    x[::17] = 0.0
+    x[5::29, 0] = np.nan
+    x.setflags(write=False)
+    return x
+
+
+# (rows, n, threshold, seed) by what the rows x event_blocks(n) entries reach in the scan
+SCALE_CASES = {
+    "two-waves": (129, 64, 2.0, 129),           # 516 entries: wave 1 of the first trip
+    "full-trip": (2048, 64, 2.0, 2048),         # 8192: exactly one trip
+    "second-trip": (2049, 64, 2.0, 2049),       # 8196: a second trip of 4 entries
+    "short-below-trip": (2730, 5, 1.0, 2730),   # 8190: 3 entries per row (windows 1, 2, 4)
+    "short-above-trip": (2731, 5, 1.0, 2731),   # 8193
+    "three-trips": (4500, 16, 2.0, 4500),       # 18000
+    "long-rows": (1200, 4101, 3.0, 1200),       # 8400: 7 workgroups per row (3 + 2 + 1 + 1)
+    "grid-cap": (32771, 8, 1.5, 32771),         # two batches forced by MAX_BATCH
+}
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(name):
+    """(the rows, their events in delivery order) of a SCALE_CASES entry, computed once."""
+    rows, n, threshold, seed = SCALE_CASES[name]
+    x = many_rows(rows, n, seed)
+    want = events_of(x, threshold)
+    want.setflags(write=False)
+    return x, want
+
+
+def window_counts(events, rows):
+    """Events per (row, window) as a rows x 4 int64 array (rows labelled 0 .. rows - 1)."""
+    c = np.zeros((rows, 4), np.int64)
+    np.add.at(c, (events["row"], np.log2(events["window"]).astype(np.int64)), 1)
+    return c
+
+
+def relabel(events, index):
+    """The events of rows 0 .. with ``row`` replaced by ``index[row]`` (what an index does)."""
+    out = events.copy()
+    out["row"] = np.asarray(index, np.int32)[events["row"]]
+    return out
+
+
+def batch_rows(workspace_bytes_of, rows, n, sized_for):
+    """Rows per batch pu_series_events picks with a workspace sized for ``sized_for`` rows: at
+    most MAX_BATCH, halved (rounding up) until the batch fits."""
+    per = min(rows, MAX_BATCH)
+    while per > 1 and workspace_bytes_of(per, n) > workspace_bytes_of(sized_for, n):
+        per = (per + 1) // 2
+    return per
 
 
 def plan_case():

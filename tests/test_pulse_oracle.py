@@ -127,6 +127,77 @@ def test_wrapped():
     assert po.wrapped(e, np.array([-21, 0, 0]), 100) and po.wrapped(e, np.array([0, 75]), 100)
 
 
+# ---- the many-row cases of tests/test_gpu_pulses_scale.py: what keeps a wrong scan from passing ----
+# entries = rows x event_blocks(n) against one wave (512) and one trip (8192) of event_scan_kernel
+SCALE_ENTRIES = {
+    "two-waves": lambda m: po.SCAN_WAVE < m <= po.SCAN_TRIP,
+    "full-trip": lambda m: m == po.SCAN_TRIP,
+    "second-trip": lambda m: po.SCAN_TRIP < m <= po.SCAN_TRIP + po.SCAN_WAVE,
+    "short-below-trip": lambda m: po.SCAN_TRIP - 3 < m < po.SCAN_TRIP,   # the last row ends inside trip 1
+    "short-above-trip": lambda m: po.SCAN_TRIP < m <= po.SCAN_TRIP + 3,  # ... and straddles the boundary
+    "three-trips": lambda m: 2 * po.SCAN_TRIP < m <= 3 * po.SCAN_TRIP,
+    "long-rows": lambda m: po.SCAN_TRIP < m <= 2 * po.SCAN_TRIP,
+    "grid-cap": lambda m: m > po.MAX_BATCH * 4,  # a first batch of 16 full trips, then 3 rows
+}
+
+
+def test_event_blocks():
+    assert [po.event_blocks(n) for n in (1, 5, 7, 8, 16, 64, 2048, 2049, 4101, 20011)] == [1, 3, 3, 4, 4, 4, 4, 5, 7, 20]
+
+
+@pytest.mark.parametrize("name", list(po.SCALE_CASES))
+def test_many_row_cases_can_tell_a_wrong_scan(name):
+    rows, n, threshold, _ = po.SCALE_CASES[name]
+    x, events = po.scale_case(name)
+    assert x.shape == (rows, n) and set(SCALE_ENTRIES) == set(po.SCALE_CASES)
+    assert SCALE_ENTRIES[name](rows * po.event_blocks(n)), rows * po.event_blocks(n)
+    if n < 8:
+        assert po.event_blocks(n) == 3
+    counts = po.window_counts(events, rows)
+    assert counts.sum() == len(events) > 0
+    # delivery order: row, window, start
+    key = np.stack([events["start"], events["window"], events["row"]])
+    assert np.array_equal(np.lexsort(key), np.arange(len(events)))
+    empty = (counts.sum(axis=1) == 0).mean()
+    assert 0.05 <= empty <= 0.40, empty          # offsets that do not advance, next to ones that do
+    assert not counts[::17].any() and not counts[5::29].any()  # the zero rows and the NaN rows
+    assert np.unique(counts).size >= 3, np.unique(counts)
+    per_window = counts.sum(axis=0)
+    assert per_window[0] > 0 and per_window[1] > 0
+    if n >= 64:
+        assert (per_window > 0).all(), per_window
+    if name == "long-rows":
+        assert po.event_blocks(n) == 7
+        for w in (1, 2):  # runs that start in a later workgroup of the window than its first
+            assert ((events["window"] == w) & (events["start"] >= po.EV_BLOCK)).any(), w
+        assert ((events["window"] == 1) & (events["start"] >= 2 * po.EV_BLOCK)).any()
+        assert len(events) > 8 * rows  # the wrapper's first capacity is too small
+    if name in ("second-trip", "three-trips"):
+        assert len(events) <= 8 * rows  # ... and here it is large enough
+
+
+def test_many_rows_generator():
+    x = po.many_rows(60, 64, 1)
+    assert not x[0].any() and not x[17].any() and x[1].any()
+    assert np.flatnonzero(np.isnan(x).any(axis=1)).tolist() == [5, 34]  # (row 34 is a zero row but for its NaN)
+    assert np.isnan(x[5, 0]) and not np.isnan(x[5, 1:]).any()
+    assert np.array_equal(x[1:5], po.many_rows(60, 64, 1)[1:5]) and not np.array_equal(x[1], po.many_rows(60, 64, 2)[1])
+    frac = (po.many_rows(400, 64, 3)[1:17] > 6).mean()
+    assert 0.06 < frac < 0.10, frac
+    ev0 = po.events_of(x[:3], 2.0)
+    assert np.array_equal(po.relabel(ev0, [9, 4, 7])["row"], np.array([9, 4, 7], np.int32)[ev0["row"]])
+
+
+def test_batch_rows_of_the_halving_rule():
+    """A workspace sized for 300, 7 or 1 of 2049 rows gives batches of 257, 5 and 1 rows; one
+    sized for 32768 of 32771 rows gives 32768 (the grid cap, not the workspace)."""
+    from pulsarutils import _hip
+    wsb = _hip.lib().pu_series_events_workspace_bytes
+    assert [po.batch_rows(wsb, 2049, 64, b) for b in (2049, 300, 7, 1)] == [2049, 257, 5, 1]
+    assert po.batch_rows(wsb, 32771, 8, po.MAX_BATCH) == po.MAX_BATCH
+    assert wsb(32771, 8) > wsb(po.MAX_BATCH, 8)
+
+
 def call_events(lib, series=1, rows=1, n=16, ld=16, thr=6.0, events=None, cap=0, count=1, ws=256, wsb=1 << 20):
     c = ctypes.c_int64(-7)
     vp = ctypes.c_void_p
