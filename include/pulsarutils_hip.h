@@ -768,6 +768,67 @@ int pu_ffa(const float *x, int64_t rows, int64_t ld, int64_t m, int64_t p, float
            const int32_t *widths, int64_t nwidths, const double *sigma, float *snr, int32_t *peak,
            void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ running-median detrending */
+
+/* A sliding-window median and the baseline built from it, to take red noise out of a time series
+ * before it is folded.  No reference counterpart; the definition is this project's own
+ * (tests/detrend_oracle.py restates it in numpy) and claims parity with no other package.  Every
+ * output bit is fixed by the arguments: no floating-point atomics, nothing depends on timing, on
+ * rows or on a row's position in the batch.
+ *
+ * Running median.  The width w is odd, h = (w - 1) / 2.  out[r][i] is the median of the w values
+ * x[r][clip(i + k, 0, n - 1)], k = -h .. h: the edge sample is repeated (scipy.ndimage's
+ * median_filter, mode "nearest").  The median of an odd count is an element of the window: no
+ * arithmetic.  Order: by value, -0 before +0; +-inf are ordinary values.  A window that holds any
+ * NaN gives the canonical quiet NaN (0x7fc00000, 0x7ff8000000000000), the rule np.median follows.
+ *
+ * Plan.  A width of W samples and min_points (101) give the block length d = max(1, W /
+ * min_points) and the median width w = 2 ((W / d) / 2) + 1 (integer divisions): the median runs
+ * over between min_points and 2 min_points block means, whatever W is.
+ *
+ * Baseline.  nblk = n / d >= 1 blocks; sum[b] is pu_rebin_time's float64 sum of block b (d samples
+ * added in order to 0.0), mean[b] = sum[b] / (double)d, med = the running median of mean at width
+ * w.  For sample i, in float64, every step one IEEE operation and nothing fused:
+ *     u    = (double)(2 i - d + 1) / (double)(2 d)       (block centres sit at u = 0, 1, 2 ..)
+ *     b0   = clip(floor(u), 0, nblk - 2)
+ *     t    = clip(u - b0, 0, 1)
+ *     base = med[b0] + t (med[b0 + 1] - med[b0])       for 0 < t < 1
+ *     base = med[b0] for t == 0, med[b0 + 1] for t == 1  (the median itself: m0 + (m1 - m0) need not be m1)
+ * and base = med[0] for nblk == 1.  So samples up to the first block centre take med[0] and samples
+ * from the last one on take med[nblk - 1], the n - nblk d samples of the tail among them, in every
+ * bit; for d == 1 base is med.
+ *     out[i] = (T)((double)x[i] - base)
+ * A NaN in med reaches exactly the samples that take it with a weight above 0; the sign and
+ * payload of a NaN that this arithmetic makes are unspecified.
+ *
+ * pu_running_median.  x, out: device, rows of n elements of dtype (PU_F32 or PU_F64, the same for
+ * both), ld >= n and ld_out >= n elements apart; they must not overlap.  A workgroup stages its
+ * tile of outputs plus the 2h halo, edge-clamped, in LDS as order-preserving unsigned keys and
+ * selects each output by a radix descent over the key bits, most significant first; no workspace.
+ * Only the n elements of a row of out are written.
+ * PU_EUNSUPPORTED: another dtype; w > 2047; rows x tiles above 2^31 - 1.  PU_EINVAL: rows < 0,
+ * n < 1, ld < n, ld_out < n, w < 1 or even; a NULL or misaligned pointer; rows that run beyond the
+ * address space; overlapping x and out.
+ * PU_OK without a launch for rows == 0.  All checked before any HIP call; asynchronous on stream.
+ *
+ * pu_running_median_describe: host only, no HIP call.  Fills up to n of {tile (outputs of a
+ * workgroup), lds_bytes (of a workgroup at this dtype and w), w_max (2047)}.  Errors as
+ * pu_running_median's for dtype and w; a NULL info or n < 0: PU_EINVAL.
+ *
+ * pu_detrend_apply.  x: device, rows of n elements of dtype (PU_F32 or PU_F64), ld >= n; med:
+ * device float64, rows of nblk medians, ld_med >= nblk; out: the dtype of x, ld_out >= n, and may
+ * be x itself (the same pointer and ld_out == ld; any other overlap is refused): the operation is elementwise, one read and one write per
+ * sample, 16 bytes per lane where x, out and both strides are aligned to that.
+ * PU_EUNSUPPORTED: another dtype; n above 2^51; rows x n / 256 above 2^31 - 1.  PU_EINVAL:
+ * rows < 0, n < 1, d < 1, nblk < 1, nblk != n / d, ld < n, ld_out < n, ld_med < nblk; a NULL or
+ * misaligned pointer; rows that run beyond the address space; out overlapping x without being x.  PU_OK without a launch for rows == 0.  All checked before any HIP call;
+ * asynchronous on stream. */
+int pu_running_median_describe(int dtype, int64_t w, int64_t *info, int n);
+int pu_running_median(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t w, void *out,
+                      int64_t ld_out, void *stream);
+int pu_detrend_apply(const void *x, int dtype, int64_t rows, int64_t n, int64_t ld, const double *med,
+                     int64_t ld_med, int64_t nblk, int64_t d, void *out, int64_t ld_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

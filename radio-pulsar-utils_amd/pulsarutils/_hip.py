@@ -98,6 +98,9 @@ SIGNATURES = {
                                   _vp]),
     "pu_ffa_describe": (_i32, [_i64, _i64, _i64, _i64, _i32, _vp, _i32]),
     "pu_ffa": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pu_running_median_describe": (_i32, [_i32, _i64, _vp, _i32]),
+    "pu_running_median": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "pu_detrend_apply": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "pu_stream_create_cu_masked": (_i32, [_i32, ctypes.POINTER(_vp)]),
     "pu_stream_destroy": (_i32, [_vp]),
 }

@@ -24,10 +24,14 @@ false-alarm model over the trials is built.
 A search covers a range of periods with integer downsampling factors (:func:`ffa_plan`): factor
 ``d`` sums ``d`` samples (``pu_rebin_time``, float64) and folds at base periods from ``bins_min``
 bins up to where the next factor takes over.  Each downsampled row is normalised by its own mean
-and standard deviation, nothing more.
+and standard deviation.  With ``detrend_width`` (seconds) the series first loses its red noise: a
+running-median baseline of that width (:mod:`pulsarutils.detrend`) is subtracted once, from the
+float64 series, before any downsampling.  The width must be many pulse widths, or the median
+takes the pulse for baseline and eats it.  Without it the rows are folded as they come.
 
-Known limits: no running-median detrending of red noise before the fold; integer downsampling
-factors only; no acceleration; no plots and no command-line tool.
+Known limits: detrending is off by default and its width is the caller's choice (no estimate of
+the red noise's time scale is made); integer downsampling factors only; no acceleration; no plots
+and no command-line tool.
 
 Conventions are ``periodicity``'s: numpy in -> numpy out, CUDA tensor in -> tensors out, a 1-D
 array is one row.  Importable without a GPU: :func:`ffa_tables`, :func:`trial_periods`,
@@ -262,6 +266,18 @@ def _downsampled(x64, d):
     return y.to(t.float32), sd
 
 
+def _detrended(what, x64, sample_time, detrend_width, detrend_min_points):
+    """``x64`` (float64 rows, a copy this module owns) minus its running-median baseline of
+    ``detrend_width`` seconds, in place; untouched for ``None``."""
+    if detrend_width is None:
+        return x64
+    from .detrend import _detrend_device
+    width = float(detrend_width)
+    if not width > 0:
+        raise ValueError(f"{what}: detrend_width must be positive seconds or None")
+    return _detrend_device(x64, max(1, int(np.rint(width / sample_time))), detrend_min_points, in_place=True)
+
+
 def _plan_steps(what, x, sample_time, period_min, period_max, bins_min, bins_max, min_rows):
     plan = ffa_plan(x.shape[1], sample_time, period_min, period_max, bins_min, bins_max, min_rows)
     if not plan:
@@ -282,11 +298,15 @@ def _best_widths(z, sd, p, widths):
     return best, k, peak.gather(2, k.unsqueeze(2)).squeeze(2), w
 
 
-def ffa_periodogram(series, sample_time, period_min, period_max, bins_min=240, bins_max=260, min_rows=8, widths=None):
+def ffa_periodogram(series, sample_time, period_min, period_max, bins_min=240, bins_max=260, min_rows=8, widths=None,
+                    detrend_width=None, detrend_min_points=101):
     """The S/N of one series (or a few rows) at every trial period of :func:`ffa_plan`.  Per step
     ``(d, p)`` the rows are downsampled by ``d``, normalised by their mean and standard deviation
     and scored by :func:`ffa_snr` at ``widths`` (default :func:`default_widths` ``(p)``); the last
-    trial of each base period is dropped (it is the first of the next).  Returns a dict: ``period``
+    trial of each base period is dropped (it is the first of the next).  ``detrend_width``
+    (seconds; None: none) subtracts a running-median baseline of that width first
+    (``detrend.detrend`` at ``max(1, rint(detrend_width / sample_time))`` samples and
+    ``detrend_min_points``).  Returns a dict: ``period``
     (s, ``(ntrials,)``, ascending within a step), ``snr`` (best over the widths, float32
     ``(rows, ntrials)`` or ``(ntrials,)``), ``width`` (s, of that best, the shape of ``snr``) and
     ``dsfactor`` (int64 ``(ntrials,)``)."""
@@ -294,7 +314,7 @@ def ffa_periodogram(series, sample_time, period_min, period_max, bins_min=240, b
     x, one_d, as_numpy = _series(series, "ffa_periodogram")
     sample_time = float(sample_time)
     plan = _plan_steps("ffa_periodogram", x, sample_time, period_min, period_max, bins_min, bins_max, min_rows)
-    x64 = x.to(t.float64)
+    x64 = _detrended("ffa_periodogram", x.to(t.float64), sample_time, detrend_width, detrend_min_points)
     periods, snrs, wids, dsf = [], [], [], []
     for d, p0, p1 in plan:
         z, sd = _downsampled(x64, d)
@@ -315,14 +335,16 @@ def ffa_periodogram(series, sample_time, period_min, period_max, bins_min=240, b
 
 
 def ffa_search(series, sample_time, period_min, period_max, sigma=7.0, bins_min=240, bins_max=260, min_rows=8,
-               widths=None, sift=True):
+               widths=None, sift=True, detrend_width=None, detrend_min_points=101):
     """Search a plane ``(ndm, n)`` (or one series) for pulses of periods ``period_min ..
     period_max`` seconds with the FFA.
 
     Per step ``(d, p)`` of :func:`ffa_plan` every row is downsampled, normalised and scored as in
     :func:`ffa_periodogram`; on the device a trial is kept when its best S/N over the widths is
     above ``sigma``, above its left neighbour among the step's trials and not below its right one,
-    and only those leave the device.
+    and only those leave the device.  ``detrend_width`` (seconds; None: none) subtracts a
+    running-median baseline of that width from every row first, as in :func:`ffa_periodogram`; it
+    must be many pulse widths.
 
     Returns a table, strongest first: ``period`` (s), ``freq`` (Hz), ``row``, ``snr``, ``width``
     (s, of the best boxcar), ``peak_phase`` (the phase in [0, 1) of the boxcar's centre, phase 0
@@ -337,7 +359,7 @@ def ffa_search(series, sample_time, period_min, period_max, sigma=7.0, bins_min=
     sample_time, thr = float(sample_time), float(sigma)
     n = x.shape[1]
     plan = _plan_steps("ffa_search", x, sample_time, period_min, period_max, bins_min, bins_max, min_rows)
-    x64 = x.to(t.float64)
+    x64 = _detrended("ffa_search", x.to(t.float64), sample_time, detrend_width, detrend_min_points)
     cols = {c: [] for c in ("period", "row", "snr", "width", "peak_phase", "dsfactor")}
     for d, p0, p1 in plan:
         z, sd = _downsampled(x64, d)
